@@ -24,7 +24,7 @@ image:
 	docker build -f docker/Dockerfile --build-arg VERSION=$(VERSION) -t $(IMAGE):$(VERSION) .
 
 bench: native
-	$(PYTHON) bench.py
+	$(PYTHON) bench.py --full
 
 suite: native
 	$(PYTHON) benchmarks/aibench_suite.py

@@ -51,7 +51,19 @@ itself (torch.distributed.run on 127.0.0.1, before anything touches a GPU) and e
 their code, so the line always covers the N GPUs it names; N beyond the GPUs the job can
 see (render nodes it may open, ROCR/HIP_VISIBLE_DEVICES) is refused with a non-zero exit.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--case resnet50-inf] [--sweep auto|on|off]
+A plain run measures the headline only: one worker in the ``vgpu`` mode (set-up, W warmup
+steps, K timed steps), then the line with ``value`` and ``ms_per_step``. ``--full`` adds
+everything else described above: the native, quota and parity modes and the figures derived
+from them, the sweep, the node point and the RCCL probe. ``--modes`` with more than one mode,
+``--sweep on`` and ``--node on`` therefore need ``--full``.
+
+``--dump-outputs DIR`` writes what the headline worker's last timed step returned (the
+logits of the batch, or the loss of a training case) as ``DIR/<name>.npy`` in float32. Model
+weights and inputs are seeded, so two builds run with the same arguments can be compared
+output for output.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--case resnet50-inf] [--dump-outputs DIR]
+    python bench.py --full [--sweep auto|on|off] [--modes native,vgpu,quota,parity] ...
 """
 import argparse
 import json
@@ -69,6 +81,7 @@ METRIC = ("ai-benchmark ResNet-50 ms/batch overhead vs native plugin; max vGPUs 
           "(value: ResNet-V2-50 b=50 346² fp32 inference throughput inside a split-4 vGPU, images/s)")
 SWEEP_MIN_AGGREGATE = 0.9
 SWEEP_MIN_TENANT = 0.9
+FULL_MODES = "native,vgpu,quota,parity"
 
 
 def parse(argv=None):
@@ -77,7 +90,13 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--case", default="resnet50-inf")
-    ap.add_argument("--modes", default="native,vgpu,quota,parity")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: the native, quota and parity modes, the "
+                         "sweep, the node point and the RCCL probe (a plain run times the vgpu mode only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the headline worker's last timed step returned as DIR/<name>.npy (float32)")
+    ap.add_argument("--modes", default=None,
+                    help=f"default: vgpu; with --full: {FULL_MODES}")
     ap.add_argument("--split", type=int, default=4, help="vGPUs per GPU of the headline pod (BASELINE config 2)")
     ap.add_argument("--cu-mode", default="auto", choices=["auto", "spatial", "temporal", "both", "off"])
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16"])
@@ -118,7 +137,15 @@ def parse(argv=None):
     ap.add_argument("--go", default=None, help=argparse.SUPPRESS)
     # CPU rehearsal of the multi-rank orchestration (gloo, fake devices, tiny input); not a measurement
     ap.add_argument("--cpu-rehearsal", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full and not args.worker:
+        beyond = [flag for flag, given in (("--modes with several modes", "," in (args.modes or "")),
+                                           ("--sweep on", args.sweep == "on"), ("--node on", args.node == "on")) if given]
+        if beyond:
+            ap.error(f"{', '.join(beyond)}: only with --full (a plain run measures the headline alone)")
+    if args.modes is None:
+        args.modes = FULL_MODES if args.full else "vgpu"
+    return args
 
 
 # ----------------------------------------------------------------------------- worker
@@ -275,17 +302,20 @@ def worker(args):
         barrier()
         g0 = region.device(0) if region else None
         t0 = time.perf_counter()
+        out = None
         for _ in range(args.steps):
-            runner.step()
+            out = runner.step()
         sync()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and out is not None and (rank == 0 or world == 1):
+            dump_outputs(args.dump_outputs, "loss" if case.train else "logits", out)
         g1 = region.device(0) if region else None
         ms = torch.tensor([dt * 1000.0 / args.steps], dtype=torch.float64)
         if world > 1:
             dist.all_reduce(ms, op=dist.ReduceOp.MAX)
         res = {"mode": args.mode, "ms_per_step": ms.item(), "items_per_step": runner.items_per_step,
-               "steps": args.steps, "mem_total": total,
+               "steps": args.steps, "mem_total": total, "startup": {k: round(v, 2) for k, v in phases.items()},
                "peak_allocated": torch.cuda.max_memory_allocated(device) if not cpu else 0}
         if g1:
             # The enforcement the pod actually ran under (auto mode: CU mask when the GPU is
@@ -305,6 +335,13 @@ def worker(args):
         barrier()
         dist.destroy_process_group()
     return 0
+
+
+def dump_outputs(directory, name, out):
+    """What the last timed step returned, as ``directory/<name>.npy`` in float32."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), out.detach().float().cpu().numpy())
 
 
 def rccl_probe(args, device, rank, world):
@@ -341,10 +378,17 @@ def rccl_probe(args, device, rank, world):
 # ----------------------------------------------------------------------------- parent
 
 
+def head_mode(modes):
+    """The mode whose worker gives the line its ``value`` and ``ms_per_step``."""
+    return "vgpu" if "vgpu" in modes else modes[-1]
+
+
 def worker_cmd(args, mode, result, port, dist=1, seconds=0.0, go=None):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--mode", mode, "--result-file", result,
            "--port", str(port), "--dist", str(dist), "--case", args.case, "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--dtype", args.dtype]
+    if args.dump_outputs and not go and mode == head_mode([m for m in args.modes.split(",") if m]):
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.cpu_rehearsal:
         cmd.append("--cpu-rehearsal")
     if go:
@@ -390,21 +434,36 @@ def native_env(uuid, cpu):
     return env
 
 
+# MIOpen's find (torch.backends.cudnn.benchmark) also times its reference convolution
+# (ConvDirectNaiveConvFwd) for every layer: 45-110 ms a run on a 64-CU slice, about 1 s per
+# distinct layer and 18 s per worker, on every start (this find is not cached). It never
+# wins where a tuned solver applies, as for every layer of the ResNets, so their timed
+# workers leave it out of the find: the same kernels are chosen (measured on MI355X: first
+# step 36 s -> 17 s on empty MIOpen caches, 18 s -> 0.8 s on filled ones; 38.7 ms/step and
+# the same logits either way). A value in the caller's environment wins.
+FIND_ENV = {"MIOPEN_DEBUG_CONV_DIRECT_NAIVE_CONV_FWD": "0"}
+
+
 def run_one(args, mode, env, port):
     """One timed worker (all ranks take part in its process group). Rank 0 returns the
     result dict, other ranks None."""
     fd, result = tempfile.mkstemp(prefix=f"bench-{mode}-", suffix=".json")
     os.close(fd)
+    if args.case.startswith("resnet"):
+        env = {**FIND_ENV, **env}
     try:
         t0 = time.time()
         rc = subprocess.call(worker_cmd(args, mode, result, port), env=env)
         if rc != 0:
             raise SystemExit(f"bench worker ({mode}) failed with exit code {rc}")
-        print(f"[bench] {mode}: worker done in {time.time() - t0:.0f} s", file=sys.stderr, flush=True)
+        done = f"[bench] {mode}: worker done in {time.time() - t0:.0f} s"
         if int(os.environ.get("RANK", 0)) != 0:
+            print(done, file=sys.stderr, flush=True)
             return None
         with open(result) as f:
-            return json.load(f)
+            res = json.load(f)
+        print(f"{done} (start-up {json.dumps(res.get('startup'))})", file=sys.stderr, flush=True)
+        return res
     finally:
         os.unlink(result)
 
@@ -758,7 +817,6 @@ def main(argv=None):
         return worker(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args, argv)
-    from amdvgpu.models.aibench import get_case
     from amdvgpu.plugin.kubelet_stub import NodeHarness
 
     world = int(os.environ.get("WORLD_SIZE", 1))
@@ -802,7 +860,7 @@ def main(argv=None):
         with open(os.path.join(os.environ["VGPU_BENCH_CONTRACT_DIR"], f"rank{rank}.json"), "w") as f:
             json.dump({"rank": rank, "local_rank": local, "uuid": uuid, "pods": applied}, f)
     rccl = None
-    if world > 1 and args.rccl_probe:
+    if args.full and world > 1 and args.rccl_probe:
         # an all-reduce between vGPUs of different GPUs must run at the native
         # xGMI bandwidth. Same ranks, same size: without the shim, then inside the pods.
         rccl = {"native": probe_rccl(args, native_env(uuid, cpu), port)}
@@ -814,19 +872,19 @@ def main(argv=None):
         if rank == 0 and all(isinstance(v, dict) and (v.get("busbw_GBps") or 0) > 0 for v in rccl.values()):
             rccl["vgpu_vs_native_busbw"] = round(rccl["vgpu"]["busbw_GBps"] / rccl["native"]["busbw_GBps"], 3)
     node = None
-    if args.node == "on" or (args.node == "auto" and world > 1):
+    if args.full and (args.node == "on" or (args.node == "auto" and world > 1)):
         node = node_point(args, backend, uuid, world, rank, port)
         port += 1
-    do_sweep = args.sweep == "on" or (args.sweep == "auto" and world == 1 and not cpu)
+    do_sweep = args.full and (args.sweep == "on" or (args.sweep == "auto" and world == 1 and not cpu))
     sweep_rows, max_vgpus = ([], None)
     if do_sweep:
         sweep_rows, max_vgpus = sweep(args, backend, uuid, [int(x) for x in args.sweep_tenants.split(",")])
     if rank != 0:
         return 0
 
+    from amdvgpu.models.aibench import get_case  # imports torch: after the workers, not in front of them
     case = get_case(args.case)
-    head_mode = "vgpu" if "vgpu" in results else modes[-1]
-    head = results[head_mode]
+    head = results[head_mode(modes)]
     ms = head["ms_per_step"]
     value = world * head["items_per_step"] * 1000.0 / ms
     c = contracts.get("vgpu", {})

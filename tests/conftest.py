@@ -1,5 +1,7 @@
 import json
 import os
+import pathlib
+import shutil
 import subprocess
 import sys
 import tempfile
@@ -28,6 +30,21 @@ def _build_native():
     from amdvgpu.shim.native import ensure_built
     rc = ensure_built()
     assert rc == 0, "native build failed"
+
+
+@pytest.fixture
+def tmp_path():
+    """A short per-test directory in place of pytest's own. The tests put the kubelet's and
+    the plugin's unix sockets up to three directories below it, and a socket's path holds at
+    most 107 characters (sockaddr_un): pytest's <tmp>/pytest-of-<user>/pytest-<n>/<test name>0
+    leaves too little of that when the temporary directory itself lies deep (gRPC then fails
+    to bind). /tmp stands in when even that directory's own path is long."""
+    base = tempfile.gettempdir()
+    if len(base) > 48 and os.access("/tmp", os.W_OK | os.X_OK):
+        base = "/tmp"
+    d = tempfile.mkdtemp(prefix="vg-", dir=base)
+    yield pathlib.Path(d)
+    shutil.rmtree(d, ignore_errors=True)
 
 
 @pytest.fixture

@@ -45,7 +45,7 @@ def test_bench_multi_rank_cpu_rehearsal(world, tmp_path):
     port = free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sweep-seconds", "1", "--cpu-rehearsal"]
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--sweep-seconds", "1", "--cpu-rehearsal", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", VGPU_BENCH_CONTRACT_DIR=str(tmp_path))
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -87,7 +87,7 @@ def test_node_point_survives_a_failing_rank(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--sweep-seconds", "1", "--modes", "native",
-           "--rccl-probe", "0", "--cpu-rehearsal"]
+           "--rccl-probe", "0", "--cpu-rehearsal", "--full"]
     env = dict(os.environ, OMP_NUM_THREADS="1", VGPU_BENCH_FAIL_NODE_RANK="1")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=REPO)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -102,7 +102,7 @@ def test_bench_self_launches_its_ranks(tmp_path):
     node) starts the N ranks itself: the line says n_gpus N, every rank ran its own pods
     and the node point covers all N GPUs."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--sweep-seconds", "1", "--cpu-rehearsal"]
+           "--sweep-seconds", "1", "--cpu-rehearsal", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(OMP_NUM_THREADS="1", VGPU_BENCH_CONTRACT_DIR=str(tmp_path))
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=REPO)
@@ -199,3 +199,42 @@ def test_common_window_rates_pods_while_all_run():
     assert bench.common_window([dict(a, step_done=[]), b]) is None
     late = {"items_per_step": 10, "steps": 1, "t0": 5.5, "t1": 6.0, "step_done": [6.0]}
     assert bench.common_window([a, late]) is None
+
+
+def test_plain_run_measures_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """Without --full the bench runs its headline worker only (no native / quota / parity
+    modes, no sweep, no node point), --steps is the number of timed steps, and --dump-outputs
+    writes what the last timed step returned; a second run with the same arguments gets the
+    same inputs, so the same outputs (CPU rehearsal: deterministic kernels)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env.update(OMP_NUM_THREADS="1", VGPU_BENCH_CONTRACT_DIR=str(tmp_path))
+    outs = []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+               "--cpu-rehearsal", "--dump-outputs", str(tmp_path / run)]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        r = json.loads(lines[0])
+        assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0 and r["dtype"] == "fp32"
+        assert r["value"] == pytest.approx(2 * 1000.0 / r["ms_per_step"], rel=1e-3)  # the rehearsal's batch is 2
+        for k in ("ms_per_batch_native", "overhead_pct_quota_only", "parity_split2_mem1.8", "sweep", "node",
+                  "rccl_allreduce_between_pods"):
+            assert k not in r, k
+        assert list(json.load(open(tmp_path / "rank0.json"))["pods"]) == ["vgpu"]  # one worker, the headline's
+        assert os.listdir(tmp_path / run) == ["logits.npy"]
+        outs.append(np.load(tmp_path / run / "logits.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2, 1000) and np.isfinite(outs[0]).all()
+    assert np.array_equal(outs[0], outs[1])
+
+
+def test_what_moved_behind_full_is_refused_without_it():
+    sys.path.insert(0, REPO)
+    import bench
+    assert bench.parse([]).modes == "vgpu" and bench.parse(["--full"]).modes == "native,vgpu,quota,parity"
+    for argv in (["--modes", "native,vgpu"], ["--sweep", "on"], ["--node", "on"]):
+        with pytest.raises(SystemExit):
+            bench.parse(argv)
+        bench.parse(argv + ["--full"])

@@ -33,7 +33,7 @@ pytestmark = pytest.mark.gpu
 def test_four_crowded_pods_on_stock_waits(tmp_path):
     out = tmp_path / "line.json"
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "10", "--warmup", "3",
-           "--modes", "native,vgpu", "--sweep", "on", "--sweep-tenants", "1,4", "--sweep-seconds", "5",
+           "--full", "--modes", "native,vgpu", "--sweep", "on", "--sweep-tenants", "1,4", "--sweep-seconds", "5",
            "--time-budget", "300", "--json-out", str(out)]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=420, env=env, cwd=REPO)

@@ -16,4 +16,7 @@ for r in d["sweep"]:
     if r["tenants"]==4: print({k:r.get(k) for k in ("aggregate_vs_one","min_tenant_vs_entitlement","cpus_busy","granted_pct","throttled_pct")})
 PY
 }
-run r5 ab_r5 && run head . && run head_nospread . --sweep-pod-env VGPU_CPU_SPREAD=0 && run head_nodlsym . --sweep-pod-env VGPU_HOOK_DLSYM=0 && run r5_again ab_r5
+# The sweep sits behind --full at HEAD; the older tree (a checkout of the round-5 commit,
+# built, given as OLD=<dir>) has no such option.
+OLD=${OLD:?set OLD to a built checkout of the older tree}
+run r5 $OLD && run head . --full && run head_nospread . --full --sweep-pod-env VGPU_CPU_SPREAD=0 && run head_nodlsym . --full --sweep-pod-env VGPU_HOOK_DLSYM=0 && run r5_again $OLD

@@ -27,7 +27,7 @@ if has smoke; then
 fi
 if has bench; then
   step bench
-  timeout -k 10 900 python bench.py --steps 20 --warmup 5 --json-out $OUT/bench.json > $OUT/bench.log 2>&1
+  timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 --json-out $OUT/bench.json > $OUT/bench.log 2>&1
   rc=$?; tail -3 $OUT/bench.log; [ $rc -eq 0 ] || exit $rc
 fi
 if has suite; then
