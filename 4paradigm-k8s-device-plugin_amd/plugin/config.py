@@ -57,6 +57,7 @@ class PluginConfig:
     placement: str = "spread"               # which GPU a 1-vGPU pod lands on (GetPreferredAllocation)
     duplicate_vgpus: str = "split"          # Allocate of two vGPUs of one GPU: split (one device per vGPU, as the
                                             # reference) | merge (one device, summed share) | reject
+    virtual_pci_ids: str = "on"             # split duplicates get virtual PCI bus ids and UUIDs (VGPU_VIRTUAL_PCI_IDS): on | off
     host_memory_per_vgpu: str = "auto"      # pinned host memory budget per vGPU (auto: a share of the node's RAM; 0 = unlimited)
     host_memory_fraction: float = 0.5       # of the node's RAM, what vGPU containers may pin in total (buffers + spill)
     host_memory_total: str = ""             # the node's RAM (default: /proc/meminfo MemTotal)
@@ -96,6 +97,8 @@ class PluginConfig:
             raise ValueError(f"invalid --placement option: {self.placement}")
         if self.duplicate_vgpus not in DUPLICATE_POLICIES:
             raise ValueError(f"invalid --duplicate-vgpus option: {self.duplicate_vgpus}")
+        if self.virtual_pci_ids not in ("on", "off"):
+            raise ValueError(f"invalid --virtual-pci-ids option: {self.virtual_pci_ids}")
         if self.numa_spread not in NUMA_SPREAD_MODES:
             raise ValueError(f"invalid --numa-spread option: {self.numa_spread}")
         if not -1 <= self.gpu_concurrency <= 64:
@@ -173,6 +176,10 @@ _FLAGS = [
      "with its own quota; the shim virtualises the device ordinals, VGPU_DUPLICATE_SPLIT) | merge (one device with "
      "the summed quota and CU share; VGPU_DUPLICATE_MERGED and the amd-vgpu/merged-duplicates annotation tell the "
      "container) | reject (fail Allocate)"),
+    ("--virtual-pci-ids", "virtual_pci_ids", str, ["VIRTUAL_PCI_IDS"],
+     "with --duplicate-vgpus=split: on (default) = the second and later vGPUs of a GPU report a virtual PCI bus id "
+     "(domain + 0x1000 * k) and UUID of their own, and pointers and streams report the vGPU they belong to "
+     "(VGPU_VIRTUAL_PCI_IDS=1) | off = every vGPU reports the physical GPU's ids"),
     ("--host-memory-per-vgpu", "host_memory_per_vgpu", str, ["HOST_MEMORY_PER_VGPU"],
      "pinned host memory (hipHostMalloc / hipHostRegister, and the host spill of oversubscribed vGPUs) per vGPU, "
      "e.g. 64g; auto (default) = --host-memory-fraction of the node's RAM divided among its vGPUs; "

@@ -428,6 +428,8 @@ def build_container_response(cfg, vdevs, devices_by_uuid, request_ids=None, usin
         # virtualises the device ordinals (native/src/shim/vdev_hooks.cpp). Compute stays per
         # physical GPU, with the vGPUs' shares summed (docs/ABI.md "Duplicate vGPUs").
         resp.envs["VGPU_DUPLICATE_SPLIT"] = "1"
+        # --virtual-pci-ids: the vGPUs after a GPU's first report a PCI bus id and UUID of their own
+        resp.envs["VGPU_VIRTUAL_PCI_IDS"] = "0" if getattr(cfg, "virtual_pci_ids", "on") == "off" else "1"
         resp.annotations[ANN_SPLIT] = ",".join(dups)
     elif dups:
         # --duplicate-vgpus=merge: the shim merges the vGPUs of one GPU into that device

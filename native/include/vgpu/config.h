@@ -156,6 +156,8 @@ struct Config {
   std::string lock_file = "/tmp/vgpulock/lock";  // host-PID discovery lock (reference /tmp/vgpulock/lock)
   int duplicate_merge = 1;               // merge two vGPUs of one physical GPU
   int duplicate_split = 0;               // VGPU_DUPLICATE_SPLIT: ... or keep them two devices (vdev_hooks.cpp)
+  int virtual_pci_ids = 1;               // VGPU_VIRTUAL_PCI_IDS: split vGPUs after a GPU's first report their own PCI bus id,
+                                         // UUID, pointer and stream device (0: the physical GPU's, as before)
   uint64_t host_mem_limit = 0;           // VGPU_HOST_MEMORY_LIMIT: pinned host memory, 0 = unlimited
   bool fail_open = false;                // VGPU_FAIL_OPEN: run unlimited when the region cannot be attached
   std::string device_map;                // VGPU_DEVICE_MAP ("<i>:<uuid> ...")

@@ -38,4 +38,13 @@ void normalize_uuid(const char* in, char* out, int outlen);
 int resolve_devices(const Config& cfg, const DeviceMap& map, const char* const* agent_uuids,
                     int n_agents, DeviceConfig* out);
 
+// Split duplicate vGPUs: the region slots holding their quotas come after the agents', agent
+// by agent, in map order. Fills, per agent, the number of map entries naming it (`count`) and
+// the slot its first vGPU would take (`first_slot`; meaningful where count > 1), and returns
+// the number of slots all of them would take (agents included). The region has kMaxDevices
+// slots: virtual_slot is the slot of an agent's k-th vGPU, or -1 past them (no quota of its
+// own; the agent's summed quota still guards).
+int virtual_slots(const DeviceMap& map, const char* const* agent_uuids, int n_agents, int* first_slot, int* count);
+inline int virtual_slot(int first_slot, int k) { return first_slot + k < kMaxDevices ? first_slot + k : -1; }
+
 }  // namespace vgpu

@@ -106,4 +106,22 @@ int resolve_devices(const Config& cfg, const DeviceMap& map, const char* const* 
   return n_agents;
 }
 
+int virtual_slots(const DeviceMap& map, const char* const* agent_uuids, int n_agents, int* first_slot, int* count) {
+  if (n_agents > kMaxDevices) n_agents = kMaxDevices;
+  int next = n_agents;
+  for (int a = 0; a < n_agents; a++) {
+    char au[64];
+    normalize_uuid(agent_uuids && agent_uuids[a] ? agent_uuids[a] : "", au, sizeof(au));
+    first_slot[a] = next;
+    count[a] = 0;
+    for (int j = 0; au[0] && j < map.n; j++) {
+      char mu[64];
+      normalize_uuid(map.e[j].uuid, mu, sizeof(mu));
+      if (!strcmp(mu, au)) count[a]++;
+    }
+    if (count[a] > 1) next += count[a];
+  }
+  return next;
+}
+
 }  // namespace vgpu

@@ -5,6 +5,7 @@
 // Design notes are in vgpu/region.h.
 #include "vgpu/region.h"
 
+#include <cassert>
 #include <errno.h>
 #include <fcntl.h>
 #include <signal.h>
@@ -390,6 +391,7 @@ uint64_t lower_limit(uint64_t lim, uint64_t ceil) {  // 0 = unlimited on either 
 }  // namespace
 
 Charge SharedRegion::charge(int slot, int dev, uint64_t bytes, MemKind kind) {
+  assert(dev >= 0 && dev < kMaxDevices);
   DeviceState& d = r_->dev[dev];
   for (int attempt = 0; attempt < 2; attempt++) {
     uint64_t lim = lower_limit(d.mem_limit, ceil_mem_[dev]);
@@ -432,6 +434,7 @@ void SharedRegion::force_charge(int slot, int dev, uint64_t bytes, MemKind kind)
 }
 
 void SharedRegion::uncharge(int slot, int dev, uint64_t bytes, MemKind kind) {
+  assert(dev >= 0 && dev < kMaxDevices);
   DeviceState& d = r_->dev[dev];
   // Saturating subtraction: a slot reclaimed concurrently must not underflow.
   auto sat_sub = [](std::atomic<uint64_t>& a, uint64_t v) {
@@ -450,8 +453,14 @@ void SharedRegion::uncharge(int slot, int dev, uint64_t bytes, MemKind kind) {
   if (kind == kMemSpill) sat_sub(d.spilled, bytes);
 }
 
-uint64_t SharedRegion::usage(int dev) const { return r_->dev[dev].used.load(std::memory_order_relaxed); }
-uint64_t SharedRegion::limit(int dev) const { return lower_limit(r_->dev[dev].mem_limit, ceil_mem_[dev]); }
+uint64_t SharedRegion::usage(int dev) const {
+  assert(dev >= 0 && dev < kMaxDevices);
+  return r_->dev[dev].used.load(std::memory_order_relaxed);
+}
+uint64_t SharedRegion::limit(int dev) const {
+  assert(dev >= 0 && dev < kMaxDevices);
+  return lower_limit(r_->dev[dev].mem_limit, ceil_mem_[dev]);
+}
 uint64_t SharedRegion::hbm_limit(int dev) const { return lower_limit(r_->dev[dev].hbm_limit, ceil_hbm_[dev]); }
 void SharedRegion::set_svm_vram(int slot, int dev, uint64_t bytes) {
   if (!r_ || slot < 0 || slot >= kMaxProcs || dev < 0 || dev >= kMaxDevices) return;

@@ -37,6 +37,7 @@ using namespace vgpu;
 using MallocManagedFn = hipError_t (*)(void**, size_t, unsigned int);
 using MallocAsyncFn = hipError_t (*)(void**, size_t, hipStream_t);
 using MallocFromPoolAsyncFn = hipError_t (*)(void**, size_t, hipMemPool_t, hipStream_t);
+using FreeAsyncFn = hipError_t (*)(void*, hipStream_t);
 
 namespace vgpu {
 
@@ -226,18 +227,25 @@ namespace {
 
 constexpr uint64_t kPoolSlack = 64ull << 20;
 
-bool async_admissible(hipMemPool_t pool, size_t size) {
+// `vdev`: with split duplicate vGPUs, the vGPU of the allocation's stream (-1 = no split). Its
+// physical device is the one whose pool serves the request, and its own quota slot must have
+// room as well as the GPU's (a chunk refused for either crashes the runtime alike).
+bool async_admissible(hipMemPool_t pool, size_t size, int vdev) {
   ShimState& s = shim();
   if (!s.active || size == 0) return true;
-  int hipdev = 0;
-  if (s.n_agents > 1) {
+  int hipdev = 0, vslot = -1;
+  const bool split = vdev_info(vdev, &hipdev, nullptr, &vslot);
+  if (!split && s.n_agents > 1) {
     VGPU_REAL_HIP(hipGetDevice);
     if (!real_hipGetDevice || real_hipGetDevice(&hipdev) != hipSuccess) hipdev = 0;
   }
   const int dev = hip_device_agent(hipdev);  // the region's device (agent) for the HIP device
   const uint64_t lim = s.region.limit(dev);
-  if (!lim || config().oversubscribe) return true;
-  if (s.region.usage(dev) + size + kPoolSlack <= lim) return true;
+  const uint64_t vlim = vslot >= 0 ? s.region.limit(vslot) : 0;
+  if ((!lim && !vlim) || config().oversubscribe) return true;
+  if ((!lim || s.region.usage(dev) + size + kPoolSlack <= lim) &&
+      (!vlim || s.region.usage(vslot) + size + kPoolSlack <= vlim))
+    return true;
   if (!pool) {
     VGPU_REAL_HIP(hipDeviceGetMemPool);
     if (!real_hipDeviceGetMemPool || real_hipDeviceGetMemPool(&pool, hipdev) != hipSuccess) pool = nullptr;
@@ -251,27 +259,51 @@ bool async_admissible(hipMemPool_t pool, size_t size) {
         size <= reserved - used)
       return true;  // served from memory the pool already holds (and the quota counts)
   }
-  VLOG_WARN("device %d OOM (stream-ordered): request %zu bytes, usage %lu of limit %lu", dev, size,
-            (unsigned long)s.region.usage(dev), (unsigned long)lim);
+  if (vlim && s.region.usage(vslot) + size + kPoolSlack > vlim)
+    VLOG_WARN("virtual device %d OOM (stream-ordered): request %zu bytes, usage %lu of limit %lu", vdev, size,
+              (unsigned long)s.region.usage(vslot), (unsigned long)vlim);
+  else
+    VLOG_WARN("device %d OOM (stream-ordered): request %zu bytes, usage %lu of limit %lu", dev, size,
+              (unsigned long)s.region.usage(dev), (unsigned long)lim);
   return false;
 }
 
 }  // namespace
 
+// With split duplicate vGPUs a stream-ordered allocation belongs to its stream's vGPU: admitted
+// against that vGPU's quota, pool growth inside the call charged to it (VdevChargeScope), and
+// the pointer recorded for the pointer queries (vdev_hooks.cpp).
 hipError_t hipMallocAsync(void** dev_ptr, size_t size, hipStream_t stream) {
   VGPU_REAL_HIP_T(hipMallocAsync, MallocAsyncFn);
   if (!real_hipMallocAsync) return hipErrorNotSupported;
   gate_suspend();
-  if (!async_admissible(nullptr, size)) return hipErrorOutOfMemory;
-  return real_hipMallocAsync(dev_ptr, size, stream);
+  const int vdev = vdev_ids_active() ? vdev_of_stream(stream) : -1;
+  if (!async_admissible(nullptr, size, vdev)) return hipErrorOutOfMemory;
+  if (vdev < 0) return real_hipMallocAsync(dev_ptr, size, stream);
+  const VdevChargeScope scope(vdev);
+  hipError_t e = real_hipMallocAsync(dev_ptr, size, stream);
+  if (e == hipSuccess && dev_ptr) vdev_record_ptr(*dev_ptr, size, vdev);
+  return e;
 }
 
 hipError_t hipMallocFromPoolAsync(void** dev_ptr, size_t size, hipMemPool_t mem_pool, hipStream_t stream) {
   VGPU_REAL_HIP_T(hipMallocFromPoolAsync, MallocFromPoolAsyncFn);
   if (!real_hipMallocFromPoolAsync) return hipErrorNotSupported;
   gate_suspend();
-  if (!async_admissible(mem_pool, size)) return hipErrorOutOfMemory;
-  return real_hipMallocFromPoolAsync(dev_ptr, size, mem_pool, stream);
+  const int vdev = vdev_ids_active() ? vdev_of_stream(stream) : -1;
+  if (!async_admissible(mem_pool, size, vdev)) return hipErrorOutOfMemory;
+  if (vdev < 0) return real_hipMallocFromPoolAsync(dev_ptr, size, mem_pool, stream);
+  const VdevChargeScope scope(vdev);
+  hipError_t e = real_hipMallocFromPoolAsync(dev_ptr, size, mem_pool, stream);
+  if (e == hipSuccess && dev_ptr) vdev_record_ptr(*dev_ptr, size, vdev);
+  return e;
+}
+
+hipError_t hipFreeAsync(void* dev_ptr, hipStream_t stream) {
+  VGPU_REAL_HIP_T(hipFreeAsync, FreeAsyncFn);
+  if (!real_hipFreeAsync) return hipErrorNotSupported;
+  vdev_forget_ptr(dev_ptr);
+  return real_hipFreeAsync(dev_ptr, stream);
 }
 
 hipError_t hipFree(void* ptr) {
@@ -291,6 +323,7 @@ hipError_t hipFree(void* ptr) {
     }
     if (rec.dev >= 0 && s.slot >= 0 && !s.exiting.load()) s.region.uncharge(s.slot, rec.dev, rec.size, kMemData);
   }
+  vdev_forget_ptr(ptr);  // a stream-ordered allocation freed here (split duplicate vGPUs)
   // Pinned host memory freed through hipFree is released in the ROCr free hook (hsa_hooks.cpp).
   return real_hipFree(ptr);
 }

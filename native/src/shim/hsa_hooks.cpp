@@ -121,7 +121,7 @@ class VirtualCharge {
  public:
   VirtualCharge(int dev, size_t size) : size_(size) {
     ShimState& s = shim();
-    slot_ = vdev_charge_slot(dev);
+    slot_ = vdev_charge_slot(dev, &vdev_);
     if (slot_ >= 0 && s.region.charge(s.slot, slot_, size, kMemData) != Charge::kOk) {
       VLOG_WARN("virtual device (slot %d) OOM: request %zu bytes, usage %lu of limit %lu", slot_, size,
                 (unsigned long)s.region.usage(slot_), (unsigned long)s.region.limit(slot_));
@@ -133,16 +133,25 @@ class VirtualCharge {
   }
   bool ok() const { return !failed_; }
   void commit(void* p) const {
+    if (slot_ < 0 && vdev_ < 0) return;
+    committed_ = true;
+    ShimState& s = shim();
+    std::lock_guard<std::mutex> g(s.alloc_mu);
+    s.vcharge[reinterpret_cast<uintptr_t>(p)] = VChargeRec{size_, slot_, vdev_};
+  }
+  // A vmem handle (a chunk of a HIP memory pool): no pointer yet, the charge goes with the handle.
+  void commit_handle(uint64_t handle) const {
     if (slot_ < 0) return;
     committed_ = true;
     ShimState& s = shim();
     std::lock_guard<std::mutex> g(s.alloc_mu);
-    s.vcharge[reinterpret_cast<uintptr_t>(p)] = AllocRec{size_, slot_, kMemData};
+    s.vmem_vcharge[handle] = AllocRec{size_, slot_, kMemData};
   }
 
  private:
   size_t size_;
   int slot_ = -1;
+  int vdev_ = -1;
   bool failed_ = false;
   mutable bool committed_ = false;
 };
@@ -232,7 +241,7 @@ hsa_status_t hsa_amd_memory_pool_allocate(hsa_amd_memory_pool_t pool, size_t siz
 // Split duplicate vGPUs: the allocation's charge on its virtual device goes with it.
 static void release_virtual_charge(void* ptr) {
   ShimState& s = shim();
-  AllocRec rec{0, -1, 0};
+  VChargeRec rec{0, -1, -1};
   {
     std::lock_guard<std::mutex> g(s.alloc_mu);
     if (s.vcharge.empty()) return;
@@ -241,7 +250,7 @@ static void release_virtual_charge(void* ptr) {
     rec = it->second;
     s.vcharge.erase(it);
   }
-  if (s.slot >= 0 && !s.exiting.load()) s.region.uncharge(s.slot, rec.dev, rec.size, kMemData);
+  if (rec.slot >= 0 && s.slot >= 0 && !s.exiting.load()) s.region.uncharge(s.slot, rec.slot, rec.size, kMemData);
 }
 
 // The one release path of both free entry points (ROCr accepts either for a pool or region
@@ -366,11 +375,18 @@ hsa_status_t hsa_amd_vmem_handle_create(hsa_amd_memory_pool_t pool, size_t size,
               (unsigned long)s.region.usage(dev), (unsigned long)s.region.limit(dev));
     return HSA_STATUS_ERROR_OUT_OF_RESOURCES;
   }
+  // Split duplicate vGPUs: the chunk is charged to the vGPU the pool grows for.
+  const VirtualCharge vc(dev, size);
+  if (!vc.ok()) {
+    s.region.uncharge(s.slot, dev, size, kMemData);
+    return HSA_STATUS_ERROR_OUT_OF_RESOURCES;
+  }
   hsa_status_t st = real_hsa_amd_vmem_handle_create(pool, size, type, flags, handle);
   if (st != HSA_STATUS_SUCCESS) {
     s.region.uncharge(s.slot, dev, size, kMemData);
     return st;
   }
+  vc.commit_handle(handle->handle);
   std::lock_guard<std::mutex> g(s.alloc_mu);
   s.vmem[handle->handle] = AllocRec{size, dev, kMemData};
   return st;
@@ -381,7 +397,7 @@ hsa_status_t hsa_amd_vmem_handle_release(hsa_amd_vmem_alloc_handle_t handle) {
   if (!real_hsa_amd_vmem_handle_release) return HSA_STATUS_ERROR;
   ShimState& s = shim();
   if (s.phase.load(std::memory_order_relaxed) == 2) {
-    AllocRec rec{0, -1, 0};
+    AllocRec rec{0, -1, 0}, vrec{0, -1, 0};
     {
       std::lock_guard<std::mutex> g(s.alloc_mu);
       auto it = s.vmem.find(handle.handle);
@@ -389,7 +405,13 @@ hsa_status_t hsa_amd_vmem_handle_release(hsa_amd_vmem_alloc_handle_t handle) {
         rec = it->second;
         s.vmem.erase(it);
       }
+      auto vit = s.vmem_vcharge.find(handle.handle);
+      if (vit != s.vmem_vcharge.end()) {
+        vrec = vit->second;
+        s.vmem_vcharge.erase(vit);
+      }
     }
+    if (vrec.dev >= 0 && s.slot >= 0 && !s.exiting.load()) s.region.uncharge(s.slot, vrec.dev, vrec.size, kMemData);
     if (rec.dev >= 0 && s.slot >= 0 && !s.exiting.load()) {
       s.region.uncharge(s.slot, rec.dev, rec.size, kMemData);
       notify_device_memory_freed();

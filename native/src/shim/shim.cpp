@@ -219,6 +219,7 @@ void atfork_child() {
   s.ipc.clear();
   s.host.clear();
   s.vcharge.clear();
+  s.vmem_vcharge.clear();
   svm_forget();
   svm_tenant_forget();
   for (auto& b : s.ipc_bytes) b.store(0);
@@ -512,26 +513,34 @@ void shim_init_after_hsa() {
     // Split duplicate vGPUs (vdev_hooks.cpp): each vGPU of a GPU that backs several gets a
     // region slot of its own after the agents' - agent by agent, in map order - holding its
     // quota; the agent's slot keeps the summed quota as the physical guard.
+    // (virtual_slots / virtual_slot, devmap.h: a vGPU past the region's kMaxDevices slots has
+    // no quota of its own, and the agent's summed quota still guards)
+    int first_slot[kMaxDevices], count[kMaxDevices];
+    const int want = virtual_slots(map, uuid_ptrs, s.n_agents, first_slot, count);
     int next = s.n_agents;
     for (int a = 0; a < s.n_agents; a++) {
+      if (count[a] <= 1) continue;
       char au[64];
       normalize_uuid(uuids[a], au, sizeof(au));
-      int idx[kMaxDevices], c = 0;
-      for (int j = 0; j < map.n; j++) {
+      for (int j = 0, k = 0; j < map.n; j++) {
         char mu[64];
         normalize_uuid(map.e[j].uuid, mu, sizeof(mu));
-        if (!strcmp(mu, au)) idx[c++] = map.e[j].vidx;
-      }
-      for (int k = 0; c > 1 && k < c && next < kMaxDevices; k++, next++) {
-        DeviceConfig v = cfg.dev[idx[k]];
+        if (strcmp(mu, au)) continue;
+        const int slot = virtual_slot(first_slot[a], k++);
+        if (slot < 0) break;
+        DeviceConfig v = cfg.dev[map.e[j].vidx];
         v.cu_limit_pct = 0;  // compute stays per physical GPU (the agent's slot)
         v.cu_range_begin = v.cu_range_end = -1;
         memcpy(v.uuid, uuids[a], sizeof(v.uuid) - 1);
         v.uuid[sizeof(v.uuid) - 1] = 0;
-        resolved.dev[next] = v;
+        resolved.dev[slot] = v;
+        next = slot + 1;
       }
     }
     resolved.num_devices = next;
+    if (want > kMaxDevices)
+      VLOG_WARN("duplicate vGPUs split: %d quota slots wanted, the region holds %d; the vGPUs past them have no "
+                "quota of their own", want, kMaxDevices);
     VLOG_INFO("duplicate vGPUs split: %d virtual quota slot(s)", next - s.n_agents);
   }
 

@@ -59,6 +59,13 @@ struct AllocRec {
   int kind;
 };
 
+// Split duplicate vGPUs (vdev_hooks.cpp): an allocation made on a virtual device.
+struct VChargeRec {
+  uint64_t size;
+  int slot;   // region slot charged for it (-1: none, e.g. a stream-ordered allocation the pool charged)
+  int vdev;   // the virtual device it was allocated on (-1 unknown)
+};
+
 // A spilled allocation backed by a KFD shared-virtual-memory range (spill.cpp): host RAM the
 // GPU reaches in place until it is promoted into HBM, at the same address.
 struct SvmRec {
@@ -105,7 +112,9 @@ struct ShimState {
   std::unordered_map<uintptr_t, AllocRec> managed;  // hipMallocManaged pointers charged at HIP level
   std::unordered_map<uintptr_t, AllocRec> ipc;      // IPC-attached pointers (owned by another process)
   std::unordered_map<uintptr_t, HostRec> host;      // pinned host memory (host_hooks.cpp)
-  std::unordered_map<uintptr_t, AllocRec> vcharge;  // split duplicate vGPUs: the virtual slot charged (dev = slot)
+  std::map<uintptr_t, VChargeRec> vcharge;          // split duplicate vGPUs: device pointer -> the vGPU it was
+                                                    // allocated on and the slot charged (searched by range)
+  std::unordered_map<uint64_t, AllocRec> vmem_vcharge;  // vmem handle -> the virtual slot charged (dev = slot)
   hsa_amd_memory_pool_t cpu_pools[kMaxAgentPools]{};  // global pools of the CPU agents (pinned host memory)
   int n_cpu_pools = 0;
   std::unordered_map<uintptr_t, int> queues;        // hsa_queue_t* → ordinal (under queue_mu)
@@ -311,7 +320,29 @@ int current_hip_agent();
 bool vdev_split_active();
 int vdev_to_phys(int v);
 // The region slot holding the quota of the virtual device the calling thread allocates on
-// device (agent) `dev`, or -1 (no split, or no virtual device of that agent).
-int vdev_charge_slot(int dev);
+// device (agent) `dev`, or -1 (no split, no virtual device of that agent, or a vGPU past the
+// region's slots); *vdev (may be null) gets that virtual device, -1 without split. Honours a
+// VdevChargeScope of the thread. Reads the built table only (called inside the runtime).
+int vdev_charge_slot(int dev, int* vdev = nullptr);
+// Split with virtual identities (VGPU_VIRTUAL_PCI_IDS): pointers and streams report their vGPU.
+bool vdev_ids_active();
+// The vGPU `stream` belongs to: the one it was created on, the thread's current one for the
+// null and per-thread streams; -1 without split. Typed as void*: this header has no HIP types.
+int vdev_of_stream(void* stream);
+// Physical HIP ordinal, agent and quota slot (-1 = none) of vGPU v; false without split.
+bool vdev_info(int v, int* phys, int* agent, int* slot);
+// While alive, allocations of this thread are charged to vGPU v (a stream-ordered allocation
+// on another vGPU's stream grows the pool inside the call).
+class VdevChargeScope {
+ public:
+  explicit VdevChargeScope(int v);
+  ~VdevChargeScope();
+ private:
+  int prev_;
+};
+// Records / forgets the vGPU of a pointer the HSA allocation hook did not see as such (a
+// stream-ordered allocation: a piece of a pool chunk).
+void vdev_record_ptr(void* p, size_t size, int v);
+void vdev_forget_ptr(void* p);
 
 }  // namespace vgpu

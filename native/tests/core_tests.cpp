@@ -1134,6 +1134,54 @@ static void test_kfd() {
   g_kfd_proc_root = "/sys/class/kfd/kfd/proc";
 }
 
+// Split duplicate vGPUs past the region's slots (2 GPUs x 8 vGPUs want 2 + 16 slots of 16):
+// the vGPUs past them get slot -1, and no index >= kMaxDevices reaches the region (charge /
+// limit / usage assert their bounds).
+static void test_virtual_slots() {
+  const char* uuids[2] = {"GPU-aaaa000000000001", "GPU-bbbb000000000002"};
+  std::string ms;
+  for (int i = 0; i < 16; i++) ms += std::to_string(i) + ":" + uuids[i / 8] + " ";
+  DeviceMap map;
+  CHECK(parse_device_map(ms.c_str(), &map));
+  CHECK_EQ(map.duplicates, 14);
+  int first[kMaxDevices], count[kMaxDevices];
+  CHECK_EQ(virtual_slots(map, uuids, 2, first, count), 18);
+  CHECK_EQ(first[0], 2);
+  CHECK_EQ(first[1], 10);
+  CHECK_EQ(count[0], 8);
+  CHECK_EQ(count[1], 8);
+  std::string p = tmp_region("vslots");
+  Config c = limits_cfg(0);
+  c.num_devices = kMaxDevices;
+  for (int i = 0; i < kMaxDevices; i++) c.dev[i].mem_limit = 1000;
+  SharedRegion r;
+  CHECK_EQ(r.attach(p.c_str(), &c, true), 0);
+  int s = r.register_process(getpid(), getpid(), 1);
+  CHECK(s >= 0);
+  int with_slot = 0;
+  for (int a = 0; a < 2; a++)
+    for (int k = 0; k < count[a]; k++) {
+      const int slot = virtual_slot(first[a], k);
+      CHECK(slot < kMaxDevices);
+      CHECK_EQ(slot, first[a] + k < kMaxDevices ? first[a] + k : -1);
+      if (slot < 0) continue;
+      with_slot++;
+      CHECK(r.charge(s, slot, 600, kMemData) == Charge::kOk);
+      CHECK_EQ(r.usage(slot), 600u);
+      CHECK_EQ(r.limit(slot), 1000u);
+      r.uncharge(s, slot, 600, kMemData);
+    }
+  CHECK_EQ(with_slot, 14);
+  // one GPU named once: no slot of its own
+  DeviceMap one;
+  CHECK(parse_device_map("0:GPU-aaaa000000000001", &one));
+  CHECK_EQ(virtual_slots(one, uuids, 2, first, count), 2);
+  CHECK_EQ(count[0], 1);
+  CHECK_EQ(count[1], 0);
+  r.unregister_process(s);
+  unlink(p.c_str());
+}
+
 int main(int argc, char** argv) {
   std::vector<std::pair<const char*, std::function<void()>>> tests = {
       {"parse_size", test_parse_size},
@@ -1162,6 +1210,7 @@ int main(int argc, char** argv) {
       {"hostpid_resolution", test_hostpid_resolution},
       {"board", test_board},
       {"ledger_fresh", test_ledger_fresh},
+      {"virtual_slots", test_virtual_slots},
   };
   if (argc > 1 && !strcmp(argv[1], "--list")) {
     for (auto& t : tests) printf("%s\n", t.first);

@@ -242,6 +242,17 @@ hipError_t hipGetDevicePropertiesR0600(hipDeviceProp_tR0600* prop, int d) {
   hsa_amd_memory_pool_get_info(g_dev[d].pool, HSA_AMD_MEMORY_POOL_INFO_SIZE, &total);
   prop->totalGlobalMem = total;
   prop->multiProcessorCount = 256;
+  // the PCI address and UUID, as hipDeviceGetPCIBusId / hipDeviceGetUuid give them (fake_hip_identity.cpp)
+  uint32_t bdf = 0, dom = 0;
+  hsa_agent_get_info(g_dev[d].agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_BDFID, &bdf);
+  hsa_agent_get_info(g_dev[d].agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_DOMAIN, &dom);
+  prop->pciBusID = (int)(bdf >> 8);
+  prop->pciDeviceID = (int)((bdf >> 3) & 0x1f);
+  prop->pciDomainID = (int)dom;
+  char u[64] = {0};
+  hsa_agent_get_info(g_dev[d].agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_UUID, u);
+  const char* hex = strncmp(u, "GPU-", 4) ? u : u + 4;
+  memcpy(prop->uuid.bytes, hex, strnlen(hex, sizeof(prop->uuid.bytes)));
   return hipSuccess;
 }
 
@@ -439,6 +450,32 @@ int fake_hip_device_cus(int dev) {
   uint32_t v = 0;
   hsa_agent_get_info(g_dev[dev].agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_COOPERATIVE_COMPUTE_UNIT_COUNT, &v);
   return (int)v;
+}
+
+// The fake's private state, for the entry points in fake_hip_identity.cpp.
+int fake_hip_priv_count() {
+  init();
+  return g_n;
+}
+int fake_hip_priv_current() { return t_dev; }
+int fake_hip_priv_stream_device(hipStream_t stream) { return dev_of(stream); }
+uint64_t fake_hip_priv_agent(int d) { return d >= 0 && d < g_n ? g_dev[d].agent.handle : 0; }
+uint64_t fake_hip_priv_pool(int d) { return d >= 0 && d < g_n ? g_dev[d].pool.handle : 0; }
+int fake_hip_priv_device_of_rocr(int rocr) {
+  for (int i = 0; i < g_n; i++)
+    if (g_dev[i].rocr == rocr) return i;
+  return -1;
+}
+hipError_t fake_hip_priv_new_stream(hipStream_t* stream) {
+  init();
+  FakeStream* s = new FakeStream{nullptr, t_dev};
+  if (hsa_queue_create(g_dev[t_dev].agent, 4096, HSA_QUEUE_TYPE_MULTI, nullptr, nullptr, 0, 0, &s->q) !=
+      HSA_STATUS_SUCCESS) {
+    delete s;
+    return hipErrorOutOfMemory;
+  }
+  *stream = reinterpret_cast<hipStream_t>(s);
+  return hipSuccess;
 }
 
 }  // extern "C"

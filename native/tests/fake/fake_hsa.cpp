@@ -15,6 +15,8 @@
 //   FAKE_ROCR_UUIDS     comma-separated agent UUIDs (default GPU-fa4e00000000000<i>)
 //   FAKE_ROCR_PARTS     agents per PCI address (default 1; 4 = CPX-style compute
 //                       partitions exposed as GPUs: consecutive agents share a BDF)
+//   FAKE_ROCR_REUSE     1: a freed HBM block's address is handed out again to the next
+//                       allocation of the same size (default 0: addresses are never reused)
 //   FAKE_KFD_ROOT       fake /sys/class/kfd/kfd/proc (unset: no KFD tree)
 //   FAKE_KFD_PID_OFFSET host-PID offset (default 100000)
 //   FAKE_ROCR_NO_SVM    1: no shared virtual memory (hsa_amd_svm_* refuse, SVM_SUPPORTED false)
@@ -357,6 +359,12 @@ hsa_status_t hsa_amd_memory_pool_get_info(hsa_amd_memory_pool_t pool, hsa_amd_me
 namespace {
 // Internal entry points: ROCr's exported functions never call each other through their
 // exported symbols (which the preloaded shim interposes), so neither does the fake.
+// Freed HBM blocks by size (FAKE_ROCR_REUSE), under State::mu.
+std::multimap<uint64_t, void*>& freed() {
+  static auto* m = new std::multimap<uint64_t, void*>();
+  return *m;
+}
+
 hsa_status_t pool_allocate_impl(hsa_amd_memory_pool_t pool, size_t size, void** ptr) {
   setup();
   State& s = st();
@@ -366,7 +374,15 @@ hsa_status_t pool_allocate_impl(hsa_amd_memory_pool_t pool, size_t size, void** 
   if (d < 0 && pool.handle != kCpuPool) return HSA_STATUS_ERROR_INVALID_ARGUMENT;
   if (d >= 0 && hbm_used(d) + size > s.gpus[d].hbm) return HSA_STATUS_ERROR_OUT_OF_RESOURCES;
   // Host memory is real (the application may touch pinned buffers); HBM is address space only.
-  void* p = d >= 0 ? bump(size) : mmap(nullptr, size, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+  void* p = nullptr;
+  if (d >= 0 && !freed().empty()) {  // FAKE_ROCR_REUSE: the address of a freed block of this size
+    auto it = freed().find(size);
+    if (it != freed().end()) {
+      p = it->second;
+      freed().erase(it);
+    }
+  }
+  if (!p) p = d >= 0 ? bump(size) : mmap(nullptr, size, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
   if (p == MAP_FAILED) p = nullptr;
   if (!p) return HSA_STATUS_ERROR_OUT_OF_RESOURCES;
   s.allocs[reinterpret_cast<uintptr_t>(p)] = {d, size};
@@ -387,6 +403,7 @@ hsa_status_t pool_free_impl(void* ptr) {
   if (d >= 0) {
     add_used(d, -(int64_t)it->second.second, false);
     kfd_update_vram(d);
+    if (env_u64("FAKE_ROCR_REUSE", 0)) freed().emplace(it->second.second, ptr);
   } else {
     munmap(ptr, it->second.second);
   }
@@ -690,6 +707,22 @@ int fake_rocr_queue_state(const hsa_queue_t* queue, uint32_t* mask_words8, int* 
 }
 
 // Bytes the fake runtime holds on GPU `dev` (what a real driver would report).
+// The allocation holding `p` (interior pointers too): its GPU (-1 = host memory), base and
+// size. Returns 0 when `p` is in no allocation.
+int fake_rocr_pointer_info(const void* p, int* dev, void** base, uint64_t* size) {
+  State& s = st();
+  std::lock_guard<std::mutex> g(s.mu);
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  auto it = s.allocs.upper_bound(a);
+  if (it == s.allocs.begin()) return 0;
+  --it;
+  if (a - it->first >= it->second.second) return 0;
+  if (dev) *dev = it->second.first;
+  if (base) *base = reinterpret_cast<void*>(it->first);
+  if (size) *size = it->second.second;
+  return 1;
+}
+
 uint64_t fake_rocr_used(int dev) {
   {
     std::lock_guard<std::mutex> g(st().mu);
