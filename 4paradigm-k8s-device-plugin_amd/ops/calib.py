@@ -9,6 +9,10 @@ These are the measurement instruments of the data plane:
   limiter.
 * :func:`stream_copy` 16 B/lane grid-stride copy: HBM bandwidth, or host-spill bandwidth
   when the source lives in spilled (host) memory.
+* :func:`pattern_fill` / :func:`pattern_check` / :func:`pattern_poke` word-exact fill and
+  verify at memory bandwidth (native/include/vgpu/pattern.h): integrity of buffers that the
+  spill, promotion and demotion paths move. :func:`pattern_reference` is the same
+  definition in numpy. ``vgpu-validate --conformance`` runs the same kernels in a pod.
 
 The library is required: there is no PyTorch fallback, a missing build raises.
 """
@@ -33,6 +37,12 @@ def _k():
         L.vgpu_stream_copy.restype = C.c_int
         L.vgpu_scratch_hog.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.vgpu_scratch_hog.restype = C.c_int
+        L.vgpu_pattern_fill.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p]
+        L.vgpu_pattern_fill.restype = C.c_int
+        L.vgpu_pattern_check.argtypes = [C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.vgpu_pattern_check.restype = C.c_int
+        L.vgpu_pattern_poke.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.vgpu_pattern_poke.restype = C.c_int
         _lib = L
     return _lib
 
@@ -103,3 +113,78 @@ def scratch_hog(nblocks=4096, stride=2654435761 & 0x7FFFFFFF | 1, device=None):
     if rc != 0:
         raise RuntimeError(f"vgpu_scratch_hog launch failed ({rc})")
     return out
+
+
+def pattern_reference(n_words, seed, base=0):
+    """The test pattern in pure numpy: words ``base .. base + n_words`` under ``seed`` as
+    uint32 (the definition of native/include/vgpu/pattern.h; ``base`` is a 64-bit word index)."""
+    import numpy as np
+    seed, base = int(seed), int(base)
+    if not 0 <= seed < 1 << 32 or not 0 <= base or base + int(n_words) > 1 << 64:
+        raise ValueError("seed is 32 bits, base + n_words at most 2**64")
+    m32 = np.uint64(0xFFFFFFFF)
+    idx = np.arange(int(n_words), dtype=np.uint64) + np.uint64(base)
+    vec, lane = idx >> np.uint64(2), idx & np.uint64(3)
+    # 32-bit arithmetic carried in uint64 and masked after every product and sum
+    a = (((vec & m32) ^ np.uint64(seed)) * np.uint64(0x9E3779B1)) & m32
+    a ^= a >> np.uint64(15)
+    a = (a + (((vec >> np.uint64(32)) * np.uint64(0x85EBCA77)) & m32) + np.uint64(seed)) & m32
+    a = (a * np.uint64(0xC2B2AE3D)) & m32
+    a ^= a >> np.uint64(13)
+    r = lane * np.uint64(8)
+    rot = ((a << r) | (a >> ((np.uint64(32) - r) & np.uint64(31)))) & m32
+    return ((rot + lane * np.uint64(0x9E3779B9)) & m32).astype(np.uint32)
+
+
+def _pattern_bytes(t):
+    n = t.numel() * t.element_size()
+    if not t.is_contiguous():
+        raise ValueError("the pattern kernels need a contiguous tensor")
+    if n == 0 or n % 16:
+        raise ValueError("the pattern kernels need a nonzero multiple of 16 bytes")
+    if t.data_ptr() % 16:
+        raise ValueError("the pattern kernels need a 16-byte aligned tensor")
+    return n
+
+
+def pattern_fill(t, seed, base=0):
+    """Fills tensor ``t`` (a multiple of 16 bytes): its 32-bit word k becomes
+    ``w(base + k, seed)`` (asynchronous)."""
+    import torch
+    n = _pattern_bytes(t)
+    rc = _k().vgpu_pattern_fill(C.c_void_p(t.data_ptr()), n, int(base), int(seed), _stream(torch, t.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_pattern_fill launch failed ({rc})")
+
+
+def pattern_check(t, seed, base=0):
+    """Verifies tensor ``t`` against the pattern. Returns ``(mismatches, first_index)``:
+    the number of 32-bit words that differ and the lowest such word index of ``t``
+    (``None`` when there is none). Synchronises."""
+    import torch
+    n = _pattern_bytes(t)
+    out = torch.tensor([0, -1], dtype=torch.int64, device=t.device)
+    rc = _k().vgpu_pattern_check(C.c_void_p(t.data_ptr()), n, int(base), int(seed), C.c_void_p(out.data_ptr()),
+                                 _stream(torch, t.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_pattern_check launch failed ({rc})")
+    bad, first = out.cpu().tolist()
+    return bad, (first if bad else None)
+
+
+def pattern_poke(t, indices):
+    """Flips one bit in each of the listed 32-bit words of ``t`` (asynchronous): proves that
+    :func:`pattern_check` can fail."""
+    import torch
+    words = t.numel() * t.element_size() // 4
+    indices = [int(i) for i in indices]
+    if not indices:
+        return
+    if min(indices) < 0 or max(indices) >= words:
+        raise ValueError("poke index outside the tensor")
+    idx = torch.tensor(indices, dtype=torch.int64, device=t.device)
+    rc = _k().vgpu_pattern_poke(C.c_void_p(t.data_ptr()), C.c_void_p(idx.data_ptr()), len(indices),
+                                _stream(torch, t.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_pattern_poke launch failed ({rc})")
+    torch.cuda.current_stream(t.device).synchronize()  # idx must outlive the kernel

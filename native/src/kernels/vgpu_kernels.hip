@@ -16,6 +16,9 @@
 //                     indexed, so it lives in scratch): makes ROCr allocate a large
 //                     scratch backing store behind the allocation hooks' back, which the
 //                     shim's context accounting has to pick up from KFD.
+//  * vgpu_pattern_*   word-exact fill / verify at memory bandwidth (vgpu/pattern.h; the kernels
+//                     are device_kernels.h, shared with the code object inside vgpu-validate):
+//                     integrity of buffers the spill, promotion and demotion paths move.
 //
 // C ABI, loaded with ctypes; pointers are device pointers (e.g. torch data_ptr()) and
 // `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
@@ -23,23 +26,12 @@
 
 #include <cstdint>
 
+#include "device_kernels.h"
+
 namespace {
 
-constexpr unsigned kHwRegHwId = 4;
-constexpr unsigned kHwRegXccId = 20;
-
 __global__ void __launch_bounds__(64) census_kernel(uint32_t* out, uint64_t spin_ticks) {
-  if (threadIdx.x == 0) {
-    // s_getreg_b32 immediate: id | offset << 6 | (size - 1) << 11
-    uint32_t hw = __builtin_amdgcn_s_getreg(kHwRegHwId | (0u << 6) | (31u << 11));
-    uint32_t xcc = __builtin_amdgcn_s_getreg(kHwRegXccId | (0u << 6) | (3u << 11));
-    uint32_t cu = (hw >> 8) & 0xf;
-    uint32_t sh = (hw >> 12) & 0x1;
-    uint32_t se = (hw >> 13) & 0x7;
-    out[blockIdx.x] = (xcc & 0xf) << 12 | se << 8 | sh << 4 | cu;
-    uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-    while (__builtin_amdgcn_s_memrealtime() - t0 < spin_ticks) __builtin_amdgcn_s_sleep(2);
-  }
+  vgpu_dev::census_body(out, spin_ticks);
 }
 
 __global__ void __launch_bounds__(64) spin_kernel(uint64_t spin_ticks, uint64_t* done) {
@@ -122,6 +114,34 @@ int vgpu_stream_copy(void* dst, const void* src, size_t bytes, void* stream) {
   if (blocks > 256 * 16) blocks = 256 * 16;
   if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(copy_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (u32x4*)dst, (const u32x4*)src, n);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// Fills `bytes` (multiple of 16) at dst: word k becomes w(base + k, seed) (vgpu/pattern.h).
+int vgpu_pattern_fill(void* dst, size_t bytes, uint64_t base, uint32_t seed, void* stream) {
+  if (!dst || !bytes || (bytes & 15)) return -1;
+  const uint64_t n = bytes / 16;
+  hipLaunchKernelGGL(pattern_fill, dim3(vgpu_dev::pattern_blocks(n)), dim3(vgpu_dev::kPatternBlock), 0,
+                     (hipStream_t)stream, (vgpu_dev::u32x4*)dst, n, base, seed);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// Verifies `bytes` (multiple of 16) at src against the same pattern. `out` is two device
+// uint64 the caller preset to {0, ~0}: the mismatching words and the lowest such word index.
+int vgpu_pattern_check(const void* src, size_t bytes, uint64_t base, uint32_t seed, uint64_t* out, void* stream) {
+  if (!src || !out || !bytes || (bytes & 15)) return -1;
+  const uint64_t n = bytes / 16;
+  hipLaunchKernelGGL(pattern_check, dim3(vgpu_dev::pattern_blocks(n)), dim3(vgpu_dev::kPatternBlock), 0,
+                     (hipStream_t)stream, (const vgpu_dev::u32x4*)src, n, base, seed, (unsigned long long*)out);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// Flips one bit in each of the `n` words of dst listed in idx (device array of word indices,
+// which the caller keeps inside the buffer).
+int vgpu_pattern_poke(void* dst, const uint64_t* idx, int n, void* stream) {
+  if (!dst || !idx || n <= 0) return -1;
+  hipLaunchKernelGGL(pattern_poke, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, (uint32_t*)dst,
+                     (const unsigned long long*)idx, (uint32_t)n);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

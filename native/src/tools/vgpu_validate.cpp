@@ -11,16 +11,26 @@
 //   vgpu-validate [--allowlist FILE]   exit 0 iff every visible GPU is authorised
 //   vgpu-validate --decode [FILE]      print the allow-list
 //   vgpu-validate --list               print the visible GPU UUIDs
+//   vgpu-validate --conformance [--json] [--device I] [--limits FILE] [--bytes N] [--spill] [--inject K]
+//                                      check the vGPU's limits from inside the container
+//                                      (validate_conformance.cpp): shim, quota, oom, cus, gate,
+//                                      memory, spill; exit 0 iff no check failed
+//   vgpu-validate --pattern N SEED [BASE]  print N words of the memory test pattern (vgpu/pattern.h)
 #include <dlfcn.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
 #include <cctype>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <set>
 #include <string>
 #include <vector>
+
+#include "vgpu/pattern.h"
+#include "vgpu/region_api.h"
+#include "validate.h"
 
 static std::string norm(std::string s) {
   while (!s.empty() && isspace((unsigned char)s.back())) s.pop_back();
@@ -45,6 +55,8 @@ static bool read_allowlist(const char* path, std::vector<std::string>* out) {
   fclose(f);
   return true;
 }
+
+std::string vgpu_validate::norm_uuid(std::string s) { return norm(std::move(s)); }
 
 using init_fn = hsa_status_t (*)();
 using iter_fn = hsa_status_t (*)(hsa_status_t (*)(hsa_agent_t, void*), void*);
@@ -78,9 +90,58 @@ static bool visible_gpus(std::vector<std::string>* out) {
   return true;
 }
 
+static int usage() {
+  fprintf(stderr,
+          "usage: vgpu-validate [--allowlist FILE] | --decode [FILE] | --list\n"
+          "       vgpu-validate --conformance [--json] [--device I] [--limits FILE] [--bytes N] [--spill] [--inject K]\n"
+          "       vgpu-validate --pattern N SEED [BASE]\n");
+  return 2;
+}
+
+static bool parse_u64(const char* s, uint64_t* out) {
+  char* end = nullptr;
+  if (!s || !isdigit((unsigned char)*s)) return false;
+  *out = strtoull(s, &end, 0);
+  return end && !*end;
+}
+
+// --pattern N SEED [BASE]: the host definition, one word per line (no GPU, no ROCm).
+static int print_pattern(int argc, char** argv, int i) {
+  uint64_t n = 0, seed = 0, base = 0;
+  if (i + 2 >= argc || !parse_u64(argv[i + 1], &n) || !parse_u64(argv[i + 2], &seed) || seed > 0xffffffffull ||
+      (i + 3 < argc && !parse_u64(argv[i + 3], &base)) || i + 4 < argc)
+    return usage();
+  for (uint64_t k = 0; k < n; k++) printf("%u\n", vgpu_pattern_word(base + k, (uint32_t)seed));
+  return 0;
+}
+
+static int conformance_main(int argc, char** argv) {
+  vgpu_validate::Options opt;
+  for (int i = 1; i < argc; i++) {
+    uint64_t v = 0;
+    if (!strcmp(argv[i], "--conformance")) continue;
+    if (!strcmp(argv[i], "--json")) opt.json = true;
+    else if (!strcmp(argv[i], "--spill")) opt.spill = true;
+    else if (!strcmp(argv[i], "--limits") && i + 1 < argc) opt.limits = argv[++i];
+    else if (!strcmp(argv[i], "--device") && i + 1 < argc && parse_u64(argv[i + 1], &v) && v < 64) opt.device = (int)v, i++;
+    else if (!strcmp(argv[i], "--inject") && i + 1 < argc && parse_u64(argv[i + 1], &v) && v >= 1 && v <= 4096)
+      opt.inject = (int)v, i++;
+    else if (!strcmp(argv[i], "--bytes") && i + 1 < argc) {
+      const int64_t b = vgpu_parse_size(argv[++i]);
+      if (b < 16 || (b & 15)) return usage();
+      opt.bytes = (uint64_t)b;
+    } else return usage();
+  }
+  if ((uint64_t)opt.inject * 8 > opt.bytes) return usage();  // the poked words are distinct
+  return vgpu_validate::conformance(opt);
+}
+
 int main(int argc, char** argv) {
   const char* allow = "/vgpu/allowlist";
   bool decode = false, list = false;
+  for (int i = 1; i < argc; i++)
+    if (!strcmp(argv[i], "--conformance")) return conformance_main(argc, argv);
+  if (argc > 1 && !strcmp(argv[1], "--pattern")) return print_pattern(argc, argv, 1);
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--decode")) {
       decode = true;
@@ -90,8 +151,7 @@ int main(int argc, char** argv) {
     } else if (!strcmp(argv[i], "--list")) {
       list = true;
     } else {
-      fprintf(stderr, "usage: vgpu-validate [--allowlist FILE] | --decode [FILE] | --list\n");
-      return 2;
+      return usage();
     }
   }
   std::vector<std::string> allowed;

@@ -185,6 +185,12 @@ hipError_t hipDeviceGetAttribute(int* value, hipDeviceAttribute_t attr, int d) {
     case hipDeviceAttributePciBusId: *value = (int)(bdf >> 8); return hipSuccess;
     case hipDeviceAttributePciDeviceId: *value = (int)((bdf >> 3) & 0x1f); return hipSuccess;
     case hipDeviceAttributePciDomainId: *value = (int)dom; return hipSuccess;
+    case hipDeviceAttributeMultiprocessorCount: {  // CLR: the agent's CU count (through the shim)
+      uint32_t cus = 0;
+      hsa_agent_get_info(g_dev[d].agent, (hsa_agent_info_t)HSA_AMD_AGENT_INFO_COMPUTE_UNIT_COUNT, &cus);
+      *value = (int)cus;
+      return hipSuccess;
+    }
     case hipDeviceAttributeTotalGlobalMem: {  // CLR: the pool size, saturated to an int
       size_t total = 0;
       hsa_amd_memory_pool_get_info(g_dev[d].pool, HSA_AMD_MEMORY_POOL_INFO_SIZE, &total);
@@ -466,6 +472,13 @@ int fake_hip_priv_device_of_rocr(int rocr) {
     if (g_dev[i].rocr == rocr) return i;
   return -1;
 }
+// A timed kernel on `stream` (null = the current device), for the module launches in
+// fake_hip_module.cpp; and the stream's queue (null for the null stream).
+void fake_hip_priv_submit(hipStream_t stream, uint32_t us) {
+  init();
+  submit(dev_of(stream), us, queue_of(stream));
+}
+hsa_queue_t* fake_hip_priv_stream_queue(hipStream_t stream) { return queue_of(stream); }
 hipError_t fake_hip_priv_new_stream(hipStream_t* stream) {
   init();
   FakeStream* s = new FakeStream{nullptr, t_dev};
