@@ -13,6 +13,11 @@ These are the measurement instruments of the data plane:
   verify at memory bandwidth (native/include/vgpu/pattern.h): integrity of buffers that the
   spill, promotion and demotion paths move. :func:`pattern_reference` is the same
   definition in numpy. ``vgpu-validate --conformance`` runs the same kernels in a pod.
+* :func:`cu_selftest` four-wave workgroups whose every wave runs a known-answer test of the
+  VALU, the LDS and the i8 and f16 matrix cores (native/include/vgpu/selftest.h) and records
+  the CU and SIMD it ran on: which CU of the slice, and which unit of it, computes wrong.
+  :func:`selftest_reference` is the same definition in numpy; ``vgpu-validate --conformance
+  --compute`` runs the same kernel in a pod.
 
 The library is required: there is no PyTorch fallback, a missing build raises.
 """
@@ -43,6 +48,9 @@ def _k():
         L.vgpu_pattern_check.restype = C.c_int
         L.vgpu_pattern_poke.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.vgpu_pattern_poke.restype = C.c_int
+        L.vgpu_cu_selftest.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                       C.c_void_p]
+        L.vgpu_cu_selftest.restype = C.c_int
         _lib = L
     return _lib
 
@@ -188,3 +196,145 @@ def pattern_poke(t, indices):
     if rc != 0:
         raise RuntimeError(f"vgpu_pattern_poke launch failed ({rc})")
     torch.cuda.current_stream(t.device).synchronize()  # idx must outlive the kernel
+
+
+SELFTEST_UNITS = ("valu", "lds", "mfma_i8", "mfma_f16")  # the order of a wave's four words
+SELFTEST_MAX_ROUNDS = 1024
+_M32 = 0xFFFFFFFF
+
+
+def _selftest_hash(q, seed):
+    """vgpu_pattern_hash for indices below 2**32, as uint64 carrying 32-bit values."""
+    import numpy as np
+    m32 = np.uint64(_M32)
+    a = ((np.asarray(q, dtype=np.uint64) ^ np.uint64(seed)) * np.uint64(0x9E3779B1)) & m32
+    a ^= a >> np.uint64(15)
+    a = (a + np.uint64(seed)) & m32
+    a = (a * np.uint64(0xC2B2AE3D)) & m32
+    a ^= a >> np.uint64(13)
+    return a
+
+
+def _selftest_mix(x):
+    import numpy as np
+    m32 = np.uint64(_M32)
+    x = np.asarray(x, dtype=np.uint64) & m32
+    x = x ^ (x >> np.uint64(15))
+    x = (x * np.uint64(0x85EBCA77)) & m32
+    return x ^ (x >> np.uint64(13))
+
+
+def _selftest_fold(c):
+    """fold() of a 32x32 integer matrix: position-dependent, 32-bit wrapping."""
+    import numpy as np
+    pos = (np.arange(1024, dtype=np.uint64).reshape(32, 32) * np.uint64(0x9E3779B9)) & np.uint64(_M32)
+    c32 = (np.asarray(c, dtype=np.int64) & _M32).astype(np.uint64)
+    return int(_selftest_mix(c32 + pos).sum()) & _M32
+
+
+def selftest_accumulators(seed, rounds, inject=False):
+    """The two 32x32 accumulators of the known-answer test as int64: (mfma_i8, mfma_f16).
+    Asserts what the definition promises about them: the i8 accumulator stays below 2**29,
+    every partial sum of the f16 one below 2**24, and a float32 accumulation of the f16
+    products equals the integer one."""
+    import numpy as np
+    seed, rounds = int(seed), int(rounds)
+    if not 0 <= seed <= _M32 or not 1 <= rounds <= SELFTEST_MAX_ROUNDS:
+        raise ValueError("seed is 32 bits, rounds 1..1024")
+    r = np.arange(rounds, dtype=np.uint64).reshape(-1, 1, 1)
+    idx = np.arange(32, dtype=np.uint64).reshape(1, -1, 1)
+
+    def i8(ab):  # [round][row or column][k] as int64
+        w = np.arange(8, dtype=np.uint64).reshape(1, 1, -1)
+        words = _selftest_hash(((np.uint64(2) * r + np.uint64(ab)) * np.uint64(32) + idx) * np.uint64(8) + w, seed)
+        if inject and ab == 0:
+            words[0, 0, 0] ^= np.uint64(1)
+        b = (words[..., None] >> (np.uint64(8) * np.arange(4, dtype=np.uint64))) & np.uint64(0xFF)
+        return b.astype(np.uint8).view(np.int8).astype(np.int64).reshape(rounds, 32, 32)
+
+    def f16(ab):
+        h = np.arange(2, dtype=np.uint64).reshape(1, 1, -1)
+        bits = _selftest_hash(np.uint64(0x10000) + ((np.uint64(2) * r + np.uint64(ab)) * np.uint64(32) + idx) * np.uint64(2) + h,
+                              seed)
+        e = (bits[..., None] >> (np.uint64(4) * np.arange(8, dtype=np.uint64))) & np.uint64(7)
+        return e.astype(np.int64).reshape(rounds, 32, 16) - 4
+
+    a, b = i8(0), i8(1)
+    ci = np.zeros((32, 32), dtype=np.int64)
+    for k in range(rounds):
+        ci += a[k] @ b[k].T
+        assert np.abs(ci).max() <= (k + 1) << 19
+    assert np.abs(ci).max() < 1 << 29, "the i8 accumulator left the range the definition promises"
+
+    a, b = f16(0), f16(1)
+    assert a.min() >= -4 and a.max() <= 3 and b.min() >= -4 and b.max() <= 3
+    cf = np.zeros((32, 32), dtype=np.int64)
+    cf32 = np.zeros((32, 32), dtype=np.float32)
+    a32, b32 = a.astype(np.float32), b.astype(np.float32)
+    for k in range(rounds):
+        for j in range(16):  # one product at a time: every partial sum is checked
+            cf += np.outer(a[k][:, j], b[k][:, j])
+            cf32 += np.outer(a32[k][:, j], b32[k][:, j])
+            assert np.abs(cf).max() < 1 << 24, "an f16 partial sum left the exact range of float32"
+    assert np.array_equal(cf32.astype(np.int64), cf) and np.array_equal(cf32, cf.astype(np.float32)), \
+        "the float32 accumulation of the f16 test differs from the integer one"
+    return ci, cf
+
+
+def selftest_reference(seed, rounds, inject=False):
+    """The four words of the known-answer test in pure numpy (the definition of
+    native/include/vgpu/selftest.h): a dict unit -> uint32 value, in SELFTEST_UNITS order."""
+    import numpy as np
+    ci, cf = selftest_accumulators(seed, rounds, inject)
+    m32 = np.uint64(_M32)
+    lane = np.arange(64, dtype=np.uint64)
+    x = _selftest_hash(np.uint64(0x20000) + lane, int(seed))
+    for step in range(16 * int(rounds)):
+        x = (x * np.uint64(0x9E3779B1) + np.uint64(step)) & m32
+        x ^= x >> np.uint64(15)
+    valu = int(_selftest_mix(x + lane).sum()) & _M32
+    arr = np.zeros(64, dtype=np.uint64)
+    arr[(17 * np.arange(64) + 5) & 63] = x
+    loaded = arr[np.arange(64) ^ 21]
+    lds = int(_selftest_mix(loaded + ((lane * np.uint64(0x9E3779B9)) & m32)).sum()) & _M32
+    return {"valu": valu, "lds": lds, "mfma_i8": _selftest_fold(ci), "mfma_f16": _selftest_fold(cf)}
+
+
+def decode_selftest_location(code):
+    """(xcc, se, sh, cu, simd) from a cu_selftest location word."""
+    return decode_location(int(code) & 0xFFFF) + ((int(code) >> 16) & 0x3,)
+
+
+def cu_selftest(nblocks=2048, rounds=64, seed=0x5E1F7E57, hold_us=300, inject=(), device=None):
+    """Runs the known-answer test in every wave of ``nblocks`` four-wave workgroups, each wave
+    holding its CU ``hold_us`` afterwards so that the grid spreads over the whole slice, and
+    compares every wave's four words with :func:`selftest_reference`. ``inject`` lists up to
+    64 workgroups whose wave 0 runs with a flipped input bit (it must then show in ``bad``).
+
+    Returns ``waves``, ``cus`` (the set of (xcc, se, sh, cu) covered), ``simd_pairs`` (distinct
+    (cu, simd) pairs) and ``bad``: ``{block, wave, location, units}`` for every wave whose
+    words differ from the reference, ``units`` naming those that do."""
+    import numpy as np
+    import torch
+    device = torch.device(device or "cuda")
+    nblocks, inject = int(nblocks), sorted({int(b) for b in inject})
+    if nblocks < 1 or len(inject) > 64 or (inject and not 0 <= inject[0] <= inject[-1] < nblocks):
+        raise ValueError("nblocks >= 1 and at most 64 injected workgroups inside the grid")
+    want = selftest_reference(seed, rounds)  # validates seed and rounds
+    out = torch.zeros(nblocks * 32, dtype=torch.int32, device=device)
+    bad = torch.tensor(inject, dtype=torch.int32, device=device) if inject else None
+    rc = _k().vgpu_cu_selftest(C.c_void_p(out.data_ptr()), nblocks, int(seed), int(rounds), int(hold_us),
+                               C.c_void_p(bad.data_ptr()) if inject else None, len(inject), _stream(torch, device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_cu_selftest launch failed ({rc})")
+    torch.cuda.synchronize(device)  # `bad` must outlive the kernel
+    rec = out.cpu().numpy().view(np.uint32).reshape(nblocks * 4, 8)
+    ref = np.array([want[u] for u in SELFTEST_UNITS], dtype=np.uint32)
+    differs = rec[:, 1:5] != ref
+    wrong = []
+    for w in np.flatnonzero(differs.any(axis=1) | (rec[:, 5:] != 0).any(axis=1)).tolist():
+        wrong.append({"block": w // 4, "wave": w % 4, "location": decode_selftest_location(rec[w, 0]),
+                      "units": [u for u, d in zip(SELFTEST_UNITS, differs[w]) if d]})
+    locs = np.unique(rec[:, 0]).tolist()
+    return {"waves": nblocks * 4, "cus": {decode_location(c & 0xFFFF) for c in locs}, "simd_pairs": len(locs),
+            "bad": wrong}

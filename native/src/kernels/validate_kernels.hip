@@ -1,5 +1,6 @@
 // The gfx950 code object embedded in vgpu-validate (a plain ELF, loaded with
-// hipModuleLoadData): the CU census and the pattern kernels, the same device code as
+// hipModuleLoadData): the CU census, the pattern kernels and
+// the compute known-answer test (cu_selftest), the same device code as
 // libvgpu_kernels.so (device_kernels.h).
 #include "device_kernels.h"
 

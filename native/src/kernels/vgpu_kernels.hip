@@ -19,6 +19,10 @@
 //  * vgpu_pattern_*   word-exact fill / verify at memory bandwidth (vgpu/pattern.h; the kernels
 //                     are device_kernels.h, shared with the code object inside vgpu-validate):
 //                     integrity of buffers the spill, promotion and demotion paths move.
+//  * vgpu_cu_selftest four-wave workgroups whose every wave runs the known-answer test of
+//                     vgpu/selftest.h (VALU, LDS, i8 and f16 MFMA) and records where it ran and
+//                     its four words, then holds its CU like the census: which CU, and which
+//                     unit of it, computes wrong (the kernel is device_kernels.h as well).
 //
 // C ABI, loaded with ctypes; pointers are device pointers (e.g. torch data_ptr()) and
 // `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
@@ -142,6 +146,21 @@ int vgpu_pattern_poke(void* dst, const uint64_t* idx, int n, void* stream) {
   if (!dst || !idx || n <= 0) return -1;
   hipLaunchKernelGGL(pattern_poke, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, (uint32_t*)dst,
                      (const unsigned long long*)idx, (uint32_t)n);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// `nblocks` workgroups of four waves; each wave runs the known-answer test of vgpu/selftest.h
+// under (seed, rounds), writes eight words at out[(4 * block + wave) * 8] (location with SIMD,
+// valu, lds, mfma_i8, mfma_f16, three zeros; out holds nblocks * 32 uint32) and then holds
+// `hold_us`. `bad` is a device array of `n_bad` (at most 64) workgroup indices whose wave 0 runs
+// the test with its injected input bit; it may be null when n_bad is 0.
+int vgpu_cu_selftest(uint32_t* out, int nblocks, uint32_t seed, int rounds, int hold_us, const uint32_t* bad, int n_bad,
+                     void* stream) {
+  if (!out || nblocks <= 0 || nblocks > (1 << 20) || rounds < 1 || rounds > (int)VGPU_SELFTEST_MAX_ROUNDS ||
+      hold_us < 0 || hold_us > 100000 || n_bad < 0 || n_bad > (int)VGPU_SELFTEST_MAX_BAD || (n_bad && !bad))
+    return -1;
+  hipLaunchKernelGGL(cu_selftest, dim3(nblocks), dim3(64 * vgpu_dev::kSelftestWaves), 0, (hipStream_t)stream, out, seed,
+                     (uint32_t)rounds, (uint64_t)hold_us * 100, bad, (uint32_t)n_bad);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

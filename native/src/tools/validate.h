@@ -14,6 +14,8 @@ struct Options {
   uint64_t bytes = 256ull << 20;        // --bytes N: size of the memory / spill test buffer
   bool spill = false;                   // --spill
   int inject = 0;                       // --inject K: poke K words between fill and check
+  bool compute = false;                 // --compute: the per-CU known-answer test (vgpu/selftest.h)
+  int inject_compute = 0;               // --inject-compute K: K workgroups run it with a flipped input bit
 };
 
 // Lower-case, no surrounding space, no "GPU-" prefix.

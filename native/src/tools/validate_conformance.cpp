@@ -3,13 +3,14 @@
 // The promise is the plugin's limits file (/vgpu/limits, falling back to the environment;
 // names as in docs/ABI.md). The observation is what the HIP runtime answers in this process
 // and what the shim published in the container's region (VGPU_SHARED_CACHE). The tool links
-// no GPU library: libamdhip64 is loaded with dlopen, the gfx950 code object with the census
-// and pattern kernels (src/kernels/validate_kernels.hip) is embedded in the binary and
+// no GPU library: libamdhip64 is loaded with dlopen, the gfx950 code object with the census,
+// pattern and known-answer kernels (src/kernels/validate_kernels.hip) is embedded in the binary and
 // loaded with hipModuleLoadData, and kernels are launched with hipModuleLaunchKernel, so
 // inside a pod they pass the shim's launch gate like any tenant's. Every GPU wait is a
 // stream synchronize after a bounded amount of work.
 //
-// Checks per visible HIP device: shim, quota, oom, cus, gate, memory and (--spill) spill;
+// Checks per visible HIP device: shim, quota, oom, cus, gate, memory, (--compute) compute and
+// (--spill) spill;
 // see usage() in vgpu_validate.cpp and docs/ABI.md.
 #include <dlfcn.h>
 #include <hip/hip_runtime_api.h>
@@ -28,6 +29,7 @@
 #include "vgpu/config.h"
 #include "vgpu/pattern.h"
 #include "vgpu/region_api.h"
+#include "vgpu/selftest.h"
 #include "validate.h"
 
 // src/tools/validate_blob.S: the gfx950 code object (a plain ELF)
@@ -168,6 +170,10 @@ struct Check {
     fields.emplace_back(k, "null");
     return *this;
   }
+  Check& raw(const char* k, const std::string& json) {
+    fields.emplace_back(k, json);
+    return *this;
+  }
 };
 
 struct DeviceReport {
@@ -199,7 +205,7 @@ struct Run {
   Promise promise;
   vgpu_region* region = nullptr;
   hipModule_t module = nullptr;
-  hipFunction_t f_census = nullptr, f_fill = nullptr, f_check = nullptr, f_poke = nullptr;
+  hipFunction_t f_census = nullptr, f_fill = nullptr, f_check = nullptr, f_poke = nullptr, f_selftest = nullptr;
   uint64_t launched = 0;  // kernels this process launched (what the gate must have counted)
   int period_ms = 120;
 
@@ -438,6 +444,75 @@ void check_memory(Run& r, DeviceReport& rep, uint64_t* res, hipStream_t s) {
   if (r.opt.inject > 0) c.num("injected", (uint64_t)r.opt.inject);
 }
 
+// Does the slice compute? Every wave of 2048 four-wave workgroups runs the known-answer test
+// of vgpu/selftest.h (VALU, LDS, i8 and f16 MFMA) and records the CU and SIMD it ran on; the
+// waves hold their CU afterwards like the census's, so the grid covers the slice. Every
+// wave's four words must equal the host definition's, and under an enforced CU mask the CUs
+// covered must be the ones reported, as in `cus`.
+void check_compute(Run& r, DeviceReport& rep, int dev, const Mapping& m, hipStream_t s) {
+  constexpr uint32_t kBlocks = 2048, kWaves = 4 * kBlocks, kRecord = 8, kRounds = 64, kHoldUs = 300, kMaxListed = 16;
+  static const char* const units[4] = {"valu", "lds", "mfma_i8", "mfma_f16"};
+  int reported = 0;
+  (void)r.hip.DeviceGetAttribute(&reported, hipDeviceAttributeMultiprocessorCount, dev);
+  uint32_t* out = nullptr;
+  uint32_t* bad = nullptr;
+  if (r.hip.HostMalloc((void**)&out, kWaves * kRecord * sizeof(uint32_t), 0) != hipSuccess || !out ||
+      r.hip.HostMalloc((void**)&bad, VGPU_SELFTEST_MAX_BAD * sizeof(uint32_t), 0) != hipSuccess || !bad) {
+    if (out) (void)r.hip.HostFree(out);
+    rep.add("compute", "fail").str("reason", "no pinned host memory for the known-answer test");
+    return;
+  }
+  memset(out, 0xff, kWaves * kRecord * sizeof(uint32_t));
+  // --inject-compute K: K distinct workgroups spread over the grid, the first and the last among them
+  uint32_t n_bad = (uint32_t)r.opt.inject_compute;
+  for (uint32_t j = 0; j < n_bad; j++) bad[j] = j && j + 1 == n_bad ? kBlocks - 1 : j * (kBlocks / n_bad);
+  uint32_t seed = 0xc0de0000u ^ (uint32_t)getpid(), rounds = kRounds;
+  uint64_t ticks = (uint64_t)kHoldUs * 100;
+  uint32_t want[4];
+  vgpu_selftest_expected(seed, rounds, 0, want);
+  void* args[] = {&out, &seed, &rounds, &ticks, &bad, &n_bad};
+  const double t0 = now_s();
+  const bool ran = r.launch(r.f_selftest, kBlocks, 256, s, args) && r.hip.StreamSynchronize(s) == hipSuccess;
+  const double ms = (now_s() - t0) * 1e3;
+  std::set<uint32_t> cus, pairs, bad_cus;
+  uint64_t waves = 0, bad_waves = 0;
+  std::string listed;
+  for (uint32_t w = 0; ran && w < kWaves; w++) {
+    const uint32_t* rec = out + (size_t)w * kRecord;
+    const bool wrote = rec[0] != 0xffffffffu;
+    if (wrote) {
+      waves++;
+      cus.insert(rec[0] & 0xffffu);
+      pairs.insert(rec[0]);
+    }
+    std::string which;
+    for (int u = 0; u < 4; u++)
+      if (rec[1 + u] != want[u]) which += std::string(which.empty() ? "" : ",") + "\"" + units[u] + "\"";
+    if (which.empty()) continue;
+    bad_waves++;
+    if (wrote) bad_cus.insert(rec[0] & 0xffffu);
+    if (bad_waves > kMaxListed) continue;
+    char loc[64] = "none";
+    if (wrote)
+      snprintf(loc, sizeof(loc), "%u/%u/%u/%u/%u", (rec[0] >> 12) & 0xf, (rec[0] >> 8) & 0xf, (rec[0] >> 4) & 0xf,
+               rec[0] & 0xf, (rec[0] >> 16) & 0x3);
+    listed += std::string(listed.empty() ? "" : ",") + "{\"location\":\"" + loc + "\",\"units\":[" + which + "]}";
+  }
+  (void)r.hip.HostFree(bad);
+  (void)r.hip.HostFree(out);
+  vgpu_device_info di{};
+  r.device_info(m.compute_slot, &di);
+  const bool enforced = di.cu_mode == 1 || di.cu_mode == 3;
+  const bool pass = ran && waves == kWaves && bad_waves == 0 && (!enforced || (int)cus.size() == reported);
+  Check& c = rep.add("compute", pass ? "pass" : "fail");
+  c.num("waves", waves).num("cus", cus.size()).num("reported", (uint64_t)(reported > 0 ? reported : 0));
+  c.num("simd_pairs", pairs.size()).num("rounds", rounds).num("bad_waves", bad_waves).str("mode", mode_name(di.cu_mode));
+  c.real("ms", ms);
+  if (!ran) c.str("reason", "a kernel launch or wait failed");
+  if (bad_waves) c.raw("bad", "[" + listed + "]").num("bad_cus", bad_cus.size());
+  if (n_bad) c.num("injected", n_bad);
+}
+
 // Virtual device memory: a buffer that the shim placed in host memory holds the pattern,
 // and still holds it after the shim promoted it into HBM at the same address.
 void check_spill(Run& r, DeviceReport& rep, const Mapping& m, uint64_t* res, hipStream_t s) {
@@ -504,9 +579,10 @@ void check_spill(Run& r, DeviceReport& rep, const Mapping& m, uint64_t* res, hip
   else if (!promoted && !bad_spilled) c.str("reason", "the buffer was not promoted within the bound");
 }
 
-void skip_rest(DeviceReport& rep, bool spill, const char* why) {
+void skip_rest(DeviceReport& rep, const vgpu_validate::Options& opt, const char* why) {
   for (const char* n : {"quota", "oom", "cus", "gate", "memory"}) rep.add(n, "skip").str("reason", why);
-  if (spill) rep.add("spill", "skip").str("reason", why);
+  if (opt.compute) rep.add("compute", "skip").str("reason", why);
+  if (opt.spill) rep.add("spill", "skip").str("reason", why);
 }
 
 void run_device(Run& r, DeviceReport& rep, int dev, const std::vector<std::string>& uuids) {
@@ -519,7 +595,7 @@ void run_device(Run& r, DeviceReport& rep, int dev, const std::vector<std::strin
   else if (!r.self(&me)) why = "this process has no slot in the region";
   if (why) {
     rep.add("shim", "fail").str("reason", why);
-    skip_rest(rep, r.opt.spill, "the shim is not in effect");
+    skip_rest(rep, r.opt, "the shim is not in effect");
     return;
   }
   rep.add("shim", "pass").num("slot", (uint64_t)m.memory_slot).num("pid", (uint64_t)me.pid);
@@ -528,9 +604,10 @@ void run_device(Run& r, DeviceReport& rep, int dev, const std::vector<std::strin
       r.hip.ModuleGetFunction(&r.f_census, r.module, "census") != hipSuccess ||
       r.hip.ModuleGetFunction(&r.f_fill, r.module, "pattern_fill") != hipSuccess ||
       r.hip.ModuleGetFunction(&r.f_check, r.module, "pattern_check") != hipSuccess ||
-      r.hip.ModuleGetFunction(&r.f_poke, r.module, "pattern_poke") != hipSuccess) {
+      r.hip.ModuleGetFunction(&r.f_poke, r.module, "pattern_poke") != hipSuccess ||
+      r.hip.ModuleGetFunction(&r.f_selftest, r.module, "cu_selftest") != hipSuccess) {
     rep.add("runtime", "fail").str("reason", "the embedded gfx950 code object does not load on this GPU");
-    skip_rest(rep, r.opt.spill, "no kernels");
+    skip_rest(rep, r.opt, "no kernels");
     return;
   }
   hipStream_t s = nullptr;
@@ -538,7 +615,7 @@ void run_device(Run& r, DeviceReport& rep, int dev, const std::vector<std::strin
   void* scratch = nullptr;
   if (r.hip.StreamCreate(&s) != hipSuccess || r.hip.HostMalloc((void**)&res, 2 * sizeof(uint64_t), 0) != hipSuccess ||
       r.hip.Malloc(&scratch, 4096) != hipSuccess) {
-    skip_rest(rep, r.opt.spill, "no stream or result buffer");
+    skip_rest(rep, r.opt, "no stream or result buffer");
     rep.checks[0].status = "fail";
     return;
   }
@@ -547,6 +624,7 @@ void run_device(Run& r, DeviceReport& rep, int dev, const std::vector<std::strin
   check_cus(r, rep, dev, m, s);
   check_gate(r, rep, scratch, s);
   check_memory(r, rep, res, s);
+  if (r.opt.compute) check_compute(r, rep, dev, m, s);
   if (r.opt.spill) check_spill(r, rep, m, res, s);
   (void)r.hip.Free(scratch);
   (void)r.hip.HostFree(res);
@@ -626,7 +704,7 @@ int conformance(const Options& opt) {
     rep.uuid = "GPU-" + uuids[d];
     if (r.hip.SetDevice(d) != hipSuccess) {
       rep.add("shim", "fail").str("reason", "hipSetDevice failed");
-      skip_rest(rep, opt.spill, "the device cannot be selected");
+      skip_rest(rep, opt, "the device cannot be selected");
     } else {
       run_device(r, rep, d, uuids);
     }

@@ -12,10 +12,13 @@
 //   vgpu-validate --decode [FILE]      print the allow-list
 //   vgpu-validate --list               print the visible GPU UUIDs
 //   vgpu-validate --conformance [--json] [--device I] [--limits FILE] [--bytes N] [--spill] [--inject K]
+//                 [--compute [--inject-compute K]]
 //                                      check the vGPU's limits from inside the container
 //                                      (validate_conformance.cpp): shim, quota, oom, cus, gate,
-//                                      memory, spill; exit 0 iff no check failed
+//                                      memory, compute, spill; exit 0 iff no check failed
 //   vgpu-validate --pattern N SEED [BASE]  print N words of the memory test pattern (vgpu/pattern.h)
+//   vgpu-validate --selftest-expected SEED ROUNDS [inject]
+//                                      print the four words of the compute known-answer test (vgpu/selftest.h)
 #include <dlfcn.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -30,6 +33,7 @@
 
 #include "vgpu/pattern.h"
 #include "vgpu/region_api.h"
+#include "vgpu/selftest.h"
 #include "validate.h"
 
 static std::string norm(std::string s) {
@@ -94,7 +98,9 @@ static int usage() {
   fprintf(stderr,
           "usage: vgpu-validate [--allowlist FILE] | --decode [FILE] | --list\n"
           "       vgpu-validate --conformance [--json] [--device I] [--limits FILE] [--bytes N] [--spill] [--inject K]\n"
-          "       vgpu-validate --pattern N SEED [BASE]\n");
+          "                     [--compute [--inject-compute K]]\n"
+          "       vgpu-validate --pattern N SEED [BASE]\n"
+          "       vgpu-validate --selftest-expected SEED ROUNDS [inject]\n");
   return 2;
 }
 
@@ -115,6 +121,20 @@ static int print_pattern(int argc, char** argv, int i) {
   return 0;
 }
 
+// --selftest-expected SEED ROUNDS [inject]: the host definition, one "unit word" line per unit
+// (no GPU, no ROCm).
+static int print_selftest(int argc, char** argv, int i) {
+  static const char* const units[4] = {"valu", "lds", "mfma_i8", "mfma_f16"};
+  uint64_t seed = 0, rounds = 0;
+  uint32_t words[4];
+  if (i + 2 >= argc || !parse_u64(argv[i + 1], &seed) || seed > 0xffffffffull || !parse_u64(argv[i + 2], &rounds) ||
+      rounds > VGPU_SELFTEST_MAX_ROUNDS || (i + 3 < argc && strcmp(argv[i + 3], "inject")) || i + 4 < argc)
+    return usage();
+  if (vgpu_selftest_expected((uint32_t)seed, (uint32_t)rounds, i + 3 < argc, words) != 0) return usage();
+  for (int u = 0; u < 4; u++) printf("%s %u\n", units[u], words[u]);
+  return 0;
+}
+
 static int conformance_main(int argc, char** argv) {
   vgpu_validate::Options opt;
   for (int i = 1; i < argc; i++) {
@@ -122,6 +142,10 @@ static int conformance_main(int argc, char** argv) {
     if (!strcmp(argv[i], "--conformance")) continue;
     if (!strcmp(argv[i], "--json")) opt.json = true;
     else if (!strcmp(argv[i], "--spill")) opt.spill = true;
+    else if (!strcmp(argv[i], "--compute")) opt.compute = true;
+    else if (!strcmp(argv[i], "--inject-compute") && i + 1 < argc && parse_u64(argv[i + 1], &v) && v >= 1 &&
+             v <= VGPU_SELFTEST_MAX_BAD)
+      opt.inject_compute = (int)v, i++;
     else if (!strcmp(argv[i], "--limits") && i + 1 < argc) opt.limits = argv[++i];
     else if (!strcmp(argv[i], "--device") && i + 1 < argc && parse_u64(argv[i + 1], &v) && v < 64) opt.device = (int)v, i++;
     else if (!strcmp(argv[i], "--inject") && i + 1 < argc && parse_u64(argv[i + 1], &v) && v >= 1 && v <= 4096)
@@ -133,6 +157,7 @@ static int conformance_main(int argc, char** argv) {
     } else return usage();
   }
   if ((uint64_t)opt.inject * 8 > opt.bytes) return usage();  // the poked words are distinct
+  if (opt.inject_compute && !opt.compute) return usage();
   return vgpu_validate::conformance(opt);
 }
 
@@ -142,6 +167,7 @@ int main(int argc, char** argv) {
   for (int i = 1; i < argc; i++)
     if (!strcmp(argv[i], "--conformance")) return conformance_main(argc, argv);
   if (argc > 1 && !strcmp(argv[1], "--pattern")) return print_pattern(argc, argv, 1);
+  if (argc > 1 && !strcmp(argv[1], "--selftest-expected")) return print_selftest(argc, argv, 1);
   for (int i = 1; i < argc; i++) {
     if (!strcmp(argv[i], "--decode")) {
       decode = true;
