@@ -6,7 +6,9 @@ These are the measurement instruments of the data plane:
   (XCC, SE, SH, CU) they ran on, read from HW_REG_XCC_ID / HW_REG_HW_ID. The number of
   distinct CUs observed is the spatial partition a queue is actually confined to.
 * :func:`spin` fixed-duration workgroups for duty-cycle measurements of the temporal
-  limiter.
+  limiter; :func:`spin_lds` the same holding dynamic LDS.
+* :func:`scratch_hog` lanes with a 16 KiB private array each; :func:`scratch_reference` is the
+  same computation in numpy.
 * :func:`stream_copy` 16 B/lane grid-stride copy: HBM bandwidth, or host-spill bandwidth
   when the source lives in spilled (host) memory.
 * :func:`pattern_fill` / :func:`pattern_check` / :func:`pattern_poke` word-exact fill and
@@ -18,6 +20,10 @@ These are the measurement instruments of the data plane:
   the CU and SIMD it ran on: which CU of the slice, and which unit of it, computes wrong.
   :func:`selftest_reference` is the same definition in numpy; ``vgpu-validate --conformance
   --compute`` runs the same kernel in a pod.
+
+The wrappers refuse with ValueError what the C entry points refuse with -1
+(native/include/vgpu/calib_args.h): no spin longer than a second or negative, no grid past
+2**20 workgroups, no copy of strided, misaligned, overlapping or host tensors.
 
 The library is required: there is no PyTorch fallback, a missing build raises.
 """
@@ -65,12 +71,32 @@ def _stream(torch, device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+MAX_BLOCKS = 1 << 20      # the bounds of native/include/vgpu/calib_args.h
+MAX_SPIN_US = 1000000
+MAX_LDS_BYTES = 160 * 1024
+SCRATCH_WORDS = 4096      # 16 KiB of private memory per lane
+SCRATCH_STRIDE = 2654435761 & 0x7FFFFFFF | 1
+
+
+def _grid(nblocks, spin_us=0):
+    """(nblocks, spin_us) as ints, refusing what the C entry points refuse: a spin outside
+    0..1 s (a negative one would never return) or a grid outside 1..2**20 workgroups."""
+    nblocks, spin_us = int(nblocks), int(spin_us)
+    if not 1 <= nblocks <= MAX_BLOCKS:
+        raise ValueError(f"nblocks {nblocks} outside 1..{MAX_BLOCKS}")
+    if not 0 <= spin_us <= MAX_SPIN_US:
+        raise ValueError(f"spin_us {spin_us} outside 0..{MAX_SPIN_US}")
+    return nblocks, spin_us
+
+
 def cu_census(nblocks=4096, spin_us=200, device=None):
-    """Returns the set of distinct (xcc, se, sh, cu) tuples the workgroups ran on."""
+    """Returns the set of distinct (xcc, se, sh, cu) tuples the workgroups ran on.
+    ``nblocks`` in 1..2**20 and ``spin_us`` in 0..1000000, else ValueError."""
     import torch
+    nblocks, spin_us = _grid(nblocks, spin_us)
     device = torch.device(device or "cuda")
     out = torch.zeros(nblocks, dtype=torch.int32, device=device)
-    rc = _k().vgpu_cu_census(C.c_void_p(out.data_ptr()), int(nblocks), int(spin_us), _stream(torch, device))
+    rc = _k().vgpu_cu_census(C.c_void_p(out.data_ptr()), nblocks, spin_us, _stream(torch, device))
     if rc != 0:
         raise RuntimeError(f"vgpu_cu_census launch failed ({rc})")
     torch.cuda.synchronize(device)
@@ -78,46 +104,114 @@ def cu_census(nblocks=4096, spin_us=200, device=None):
 
 
 def spin(nblocks, spin_us, device=None, counter=None):
-    """Launches ``nblocks`` workgroups spinning ``spin_us`` each (asynchronous)."""
+    """Launches ``nblocks`` workgroups spinning ``spin_us`` each (asynchronous); every
+    workgroup then adds 1 to element 0 of ``counter``, a CUDA int64 tensor, when one is given.
+    ``nblocks`` in 1..2**20 and ``spin_us`` in 0..1000000, else ValueError."""
     import torch
+    nblocks, spin_us = _grid(nblocks, spin_us)
+    if counter is not None:
+        if not isinstance(counter, torch.Tensor) or counter.dtype != torch.int64:
+            raise ValueError("the counter must be an int64 tensor")
+        if counter.numel() < 1:
+            raise ValueError("the counter needs at least one element")
+        if not counter.is_cuda:
+            raise ValueError("the counter must be a CUDA tensor")
     device = torch.device(device or "cuda")
     ptr = C.c_void_p(counter.data_ptr()) if counter is not None else None
-    rc = _k().vgpu_spin(int(nblocks), int(spin_us), ptr, _stream(torch, device))
+    rc = _k().vgpu_spin(nblocks, spin_us, ptr, _stream(torch, device))
     if rc != 0:
         raise RuntimeError(f"vgpu_spin launch failed ({rc})")
 
 
 def spin_lds(nblocks, spin_us, lds_bytes, device=None):
     """Launches ``nblocks`` workgroups spinning ``spin_us`` each while holding
-    ``lds_bytes`` of LDS (asynchronous): a grid dispatched over many rounds."""
+    ``lds_bytes`` of LDS (asynchronous): a grid dispatched over many rounds.
+    ``nblocks`` in 1..2**20, ``spin_us`` in 0..1000000 and ``lds_bytes`` in 1..163840 (a CU's
+    whole LDS), else ValueError."""
     import torch
+    nblocks, spin_us = _grid(nblocks, spin_us)
+    lds_bytes = int(lds_bytes)
+    if not 1 <= lds_bytes <= MAX_LDS_BYTES:
+        raise ValueError(f"lds_bytes {lds_bytes} outside 1..{MAX_LDS_BYTES}")
     device = torch.device(device or "cuda")
-    rc = _k().vgpu_spin_lds(int(nblocks), int(spin_us), int(lds_bytes), _stream(torch, device))
+    rc = _k().vgpu_spin_lds(nblocks, spin_us, lds_bytes, _stream(torch, device))
     if rc != 0:
         raise RuntimeError(f"vgpu_spin_lds launch failed ({rc})")
 
 
 def stream_copy(dst, src, nbytes=None):
-    """Copies ``nbytes`` (default: all of src) from tensor src to tensor dst (asynchronous)."""
+    """Copies ``nbytes`` (default: all of src) from tensor src to tensor dst (asynchronous).
+
+    Both are contiguous CUDA tensors of one device whose ``data_ptr()`` is 16-byte aligned and
+    whose byte ranges do not overlap (the kernel's pointers are ``__restrict__``); ``nbytes`` is
+    a multiple of 16 that fits both, and 0 copies nothing. Anything else is a ValueError."""
     import torch
-    n = int(nbytes if nbytes is not None else src.numel() * src.element_size())
-    if n > dst.numel() * dst.element_size() or n > src.numel() * src.element_size():
+    dst_bytes, src_bytes = dst.numel() * dst.element_size(), src.numel() * src.element_size()
+    n = int(nbytes if nbytes is not None else src_bytes)
+    if n < 0:
+        raise ValueError("stream_copy of a negative size")
+    if n > dst_bytes or n > src_bytes:
         raise ValueError("copy larger than a buffer")
     if n % 16:
         raise ValueError("stream_copy needs a multiple of 16 bytes")
+    if not dst.is_contiguous() or not src.is_contiguous():
+        raise ValueError("stream_copy needs contiguous tensors")
+    if dst.data_ptr() % 16 or src.data_ptr() % 16:
+        raise ValueError("stream_copy needs 16-byte aligned tensors")
+    if dst.data_ptr() < src.data_ptr() + n and src.data_ptr() < dst.data_ptr() + n:
+        raise ValueError("stream_copy of overlapping byte ranges")
+    if not dst.is_cuda or not src.is_cuda:
+        raise ValueError("stream_copy needs CUDA tensors")
+    if dst.device != src.device:
+        raise ValueError("stream_copy between tensors on different devices")
+    if n == 0:
+        return
     rc = _k().vgpu_stream_copy(C.c_void_p(dst.data_ptr()), C.c_void_p(src.data_ptr()), n, _stream(torch, dst.device))
     if rc != 0:
         raise RuntimeError(f"vgpu_stream_copy launch failed ({rc})")
 
 
-def scratch_hog(nblocks=4096, stride=2654435761 & 0x7FFFFFFF | 1, device=None):
+def scratch_reference(stride=SCRATCH_STRIDE):
+    """The 64 checksums one workgroup of :func:`scratch_hog` writes, as uint32, simulated
+    literally from scratch_kernel in numpy: each lane fills its 4096-word private array with
+    ``buf[(i * stride + lane) % 4096] = i ^ lane`` for i in 0..4095 and then sums
+    ``buf[(i * stride) % 4096]`` over i = 0, 7, 14, ..., all in 32-bit arithmetic."""
+    import numpy as np
+    stride = int(stride)
+    if not 1 <= stride <= 0x7FFFFFFF or not stride & 1:
+        raise ValueError("stride is odd and in 1..2**31-1")
+    m32 = np.uint64(0xFFFFFFFF)
+    words = np.uint64(SCRATCH_WORDS)
+    lane = np.arange(64, dtype=np.uint64)
+    rows = np.arange(64)
+    buf = np.zeros((64, SCRATCH_WORDS), dtype=np.uint64)
+    written = np.zeros((64, SCRATCH_WORDS), dtype=bool)
+    for i in range(SCRATCH_WORDS):  # in the kernel's order: a later write to a word wins
+        at = ((((np.uint64(i) * np.uint64(stride)) & m32) + lane) & m32) % words
+        buf[rows, at] = np.uint64(i) ^ lane
+        written[rows, at] = True
+    acc = np.zeros(64, dtype=np.uint64)
+    for i in range(0, SCRATCH_WORDS, 7):
+        at = int(((np.uint64(i) * np.uint64(stride)) & m32) % words)
+        assert written[:, at].all(), "the kernel would read a word it never wrote"
+        acc = (acc + buf[:, at]) & m32
+    return acc.astype(np.uint32)
+
+
+def scratch_hog(nblocks=4096, stride=SCRATCH_STRIDE, device=None):
     """Runs a kernel whose lanes each hold a 16 KiB private (scratch) array; returns the
-    per-lane checksums. ROCr backs the private segment with a scratch allocation that
-    never passes the allocation hooks (the shim accounts it from KFD's VRAM counter)."""
+    per-lane checksums, 64 int32 per workgroup whose bits are :func:`scratch_reference`. ROCr
+    backs the private segment with a scratch allocation that never passes the allocation hooks
+    (the shim accounts it from KFD's VRAM counter). ``nblocks`` in 1..2**20 and ``stride`` odd
+    and in 1..2**31-1, else ValueError."""
     import torch
+    nblocks, _ = _grid(nblocks)
+    stride = int(stride)
+    if not 1 <= stride <= 0x7FFFFFFF or not stride & 1:
+        raise ValueError("stride is odd and in 1..2**31-1")
     device = torch.device(device or "cuda")
     out = torch.empty(nblocks * 64, dtype=torch.int32, device=device)
-    rc = _k().vgpu_scratch_hog(C.c_void_p(out.data_ptr()), int(nblocks), int(stride), _stream(torch, device))
+    rc = _k().vgpu_scratch_hog(C.c_void_p(out.data_ptr()), nblocks, stride, _stream(torch, device))
     if rc != 0:
         raise RuntimeError(f"vgpu_scratch_hog launch failed ({rc})")
     return out

@@ -9,7 +9,8 @@
 //                     the spatial partition actually enforced.
 //  * vgpu_spin        fixed-duration workgroups (s_memrealtime, 100 MHz) for
 //                     duty-cycle / temporal-limit measurements; vgpu_spin_lds the
-//                     same holding dynamic LDS (few workgroups per CU at a time).
+//                     same holding dynamic LDS (few workgroups per CU at a time). A spin
+//                     lasts 0 .. 1 s: nothing longer, and nothing negative, is launched.
 //  * vgpu_stream_copy 16-byte-per-lane grid-stride copy; with the source in spilled
 //                     host memory it measures the oversubscription path's bandwidth.
 //  * vgpu_scratch_hog a kernel with a 16 KiB-per-lane private segment (dynamically
@@ -25,12 +26,16 @@
 //                     unit of it, computes wrong (the kernel is device_kernels.h as well).
 //
 // C ABI, loaded with ctypes; pointers are device pointers (e.g. torch data_ptr()) and
-// `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream).
+// `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream). What each entry point
+// accepts is vgpu/calib_args.h (host-only, tested in tests/core_tests.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "device_kernels.h"
+#include "vgpu/calib_args.h"
+
+namespace calib = vgpu::calib;
 
 namespace {
 
@@ -78,45 +83,53 @@ __global__ void __launch_bounds__(256) copy_kernel(u32x4* __restrict__ dst, cons
 
 extern "C" {
 
+// The argument rules are vgpu/calib_args.h: every entry point below returns -1, before any HIP
+// call, for what they refuse (nblocks outside 1..2^20, spin_us outside 0..1000000, ...), 0 after
+// a launch and -2 when the launch failed. The ticks a kernel spins come from the clamped spin_us.
+
 // Launches `nblocks` single-wave workgroups that each spin `spin_us` microseconds and
 // write their location code to out[block] (device buffer of nblocks uint32).
 int vgpu_cu_census(uint32_t* out, int nblocks, int spin_us, void* stream) {
-  if (!out || nblocks <= 0) return -1;
+  if (!calib::census_args_ok(out, nblocks, spin_us)) return -1;
   hipLaunchKernelGGL(census_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, out,
-                     (uint64_t)spin_us * 100);
+                     calib::spin_ticks(spin_us));
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// `nblocks` single-wave workgroups spinning `spin_us` each; lane 0 of each then adds 1 to the
+// device uint64 `done`, which may be null.
 int vgpu_spin(int nblocks, int spin_us, uint64_t* done, void* stream) {
-  if (nblocks <= 0) return -1;
-  hipLaunchKernelGGL(spin_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, (uint64_t)spin_us * 100, done);
+  if (!calib::spin_args_ok(nblocks, spin_us)) return -1;
+  hipLaunchKernelGGL(spin_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, calib::spin_ticks(spin_us), done);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// `nblocks` single-wave workgroups spinning `spin_us` each while holding `lds_bytes` of LDS.
+// `nblocks` single-wave workgroups spinning `spin_us` each while holding `lds_bytes`
+// (1..163840, a CU's whole LDS) of dynamic LDS.
 int vgpu_spin_lds(int nblocks, int spin_us, int lds_bytes, void* stream) {
-  if (nblocks <= 0 || lds_bytes < 1 || lds_bytes > 160 * 1024) return -1;
+  if (!calib::spin_lds_args_ok(nblocks, spin_us, lds_bytes)) return -1;
   hipLaunchKernelGGL(spin_lds_kernel, dim3(nblocks), dim3(64), (size_t)lds_bytes, (hipStream_t)stream,
-                     (uint64_t)spin_us * 100);
+                     calib::spin_ticks(spin_us));
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
 // `nblocks` single-wave workgroups, each lane with a 16 KiB private array; out holds
-// nblocks * 64 uint32. `stride` must be odd (any odd value gives a permutation).
+// nblocks * 64 uint32. `stride` must be odd and positive (any odd value gives a permutation).
 int vgpu_scratch_hog(uint32_t* out, int nblocks, int stride, void* stream) {
-  if (!out || nblocks <= 0 || !(stride & 1)) return -1;
+  if (!calib::scratch_args_ok(out, nblocks, stride)) return -1;
   hipLaunchKernelGGL(scratch_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, out, (uint32_t)stride);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-// Copies `bytes` (multiple of 16) from src to dst.
+// Copies `bytes` (a multiple of 16) from src to dst: both 16-byte aligned, not overlapping.
+// Zero bytes launch nothing.
 int vgpu_stream_copy(void* dst, const void* src, size_t bytes, void* stream) {
-  if (!dst || !src || (bytes & 15)) return -1;
+  const calib::CopyArgs args = calib::copy_args(dst, src, bytes);
+  if (args != calib::kCopyLaunch) return args;
   size_t n = bytes / 16;
   // >> 256 CUs x 8 waves: enough workgroups in flight to saturate HBM / the link.
   int blocks = (int)((n + 255) / 256);
   if (blocks > 256 * 16) blocks = 256 * 16;
-  if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(copy_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (u32x4*)dst, (const u32x4*)src, n);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "vgpu/board.h"
+#include "vgpu/calib_args.h"
 #include "vgpu/config.h"
 #include "vgpu/cumask.h"
 #include "vgpu/devmap.h"
@@ -1182,6 +1183,65 @@ static void test_virtual_slots() {
   unlink(p.c_str());
 }
 
+// The argument rules of the calibration entry points (vgpu/calib_args.h), at both sides of
+// every bound: what these refuse, libvgpu_kernels.so never launches.
+static void test_calib_args() {
+  namespace c = vgpu::calib;
+  alignas(16) static unsigned char mem[64];
+  void* p = mem;
+  CHECK(!c::blocks_ok(INT32_MIN) && !c::blocks_ok(-1) && !c::blocks_ok(0) && c::blocks_ok(1));
+  CHECK(c::blocks_ok(1 << 20) && !c::blocks_ok((1 << 20) + 1) && !c::blocks_ok(INT32_MAX));
+  CHECK(!c::spin_us_ok(INT32_MIN) && !c::spin_us_ok(-1) && c::spin_us_ok(0));
+  CHECK(c::spin_us_ok(1000000) && !c::spin_us_ok(1000001) && !c::spin_us_ok(INT32_MAX));
+
+  // ticks: 100 per microsecond, from the clamped value, so never more than 10^8 (one second)
+  CHECK_EQ(c::spin_ticks(0), 0u);
+  CHECK_EQ(c::spin_ticks(1), 100u);
+  CHECK_EQ(c::spin_ticks(20000), 2000000u);
+  CHECK_EQ(c::spin_ticks(1000000), 100000000u);
+  CHECK_EQ(c::spin_ticks(1000001), 100000000u);
+  CHECK_EQ(c::spin_ticks(INT32_MAX), 100000000u);
+  CHECK_EQ(c::spin_ticks(-1), 0u);
+  CHECK_EQ(c::spin_ticks(INT32_MIN), 0u);
+
+  CHECK(c::census_args_ok(p, 1, 0) && c::census_args_ok(p, 1 << 20, 1000000));
+  CHECK(!c::census_args_ok(nullptr, 1, 0));
+  CHECK(!c::census_args_ok(p, 0, 0) && !c::census_args_ok(p, (1 << 20) + 1, 0));
+  CHECK(!c::census_args_ok(p, 1, -1) && !c::census_args_ok(p, 1, INT32_MIN) && !c::census_args_ok(p, 1, 1000001));
+
+  CHECK(c::spin_args_ok(1, 0) && c::spin_args_ok(1 << 20, 1000000));
+  CHECK(!c::spin_args_ok(0, 10) && !c::spin_args_ok(-1, 10) && !c::spin_args_ok((1 << 20) + 1, 10));
+  CHECK(!c::spin_args_ok(1, -1) && !c::spin_args_ok(1, INT32_MIN) && !c::spin_args_ok(1, 1000001));
+
+  CHECK(c::spin_lds_args_ok(1, 0, 1) && c::spin_lds_args_ok(1 << 20, 1000000, 163840));
+  CHECK(!c::spin_lds_args_ok(1, 0, 0) && !c::spin_lds_args_ok(1, 0, -1) && !c::spin_lds_args_ok(1, 0, 163841));
+  CHECK(!c::spin_lds_args_ok(1, 0, INT32_MIN) && !c::spin_lds_args_ok(1, 0, INT32_MAX));
+  CHECK(!c::spin_lds_args_ok(0, 0, 1024) && !c::spin_lds_args_ok((1 << 20) + 1, 0, 1024));
+  CHECK(!c::spin_lds_args_ok(1, -1, 1024) && !c::spin_lds_args_ok(1, INT32_MIN, 1024) &&
+        !c::spin_lds_args_ok(1, 1000001, 1024));
+
+  CHECK(c::scratch_args_ok(p, 1, 1) && c::scratch_args_ok(p, 1 << 20, INT32_MAX) && c::scratch_args_ok(p, 1, 3));
+  CHECK(!c::scratch_args_ok(nullptr, 1, 1));
+  CHECK(!c::scratch_args_ok(p, 0, 1) && !c::scratch_args_ok(p, (1 << 20) + 1, 1));
+  CHECK(!c::scratch_args_ok(p, 1, 0) && !c::scratch_args_ok(p, 1, 2) && !c::scratch_args_ok(p, 1, -1));
+  CHECK(!c::scratch_args_ok(p, 1, INT32_MIN) && !c::scratch_args_ok(p, 1, INT32_MIN + 1));
+
+  CHECK_EQ(c::copy_args(mem, mem + 32, 16), c::kCopyLaunch);
+  CHECK_EQ(c::copy_args(mem, mem + 32, (size_t)1 << 40), c::kCopyLaunch);
+  CHECK_EQ(c::copy_args(mem, mem + 32, 0), c::kCopyNothing);
+  CHECK_EQ(c::copy_args(mem, mem + 32, 15), c::kCopyRefused);
+  CHECK_EQ(c::copy_args(mem, mem + 32, 17), c::kCopyRefused);
+  CHECK_EQ(c::copy_args(mem, mem + 32, 1), c::kCopyRefused);
+  CHECK_EQ(c::copy_args(nullptr, mem, 16), c::kCopyRefused);
+  CHECK_EQ(c::copy_args(mem, nullptr, 16), c::kCopyRefused);
+  CHECK_EQ(c::copy_args(nullptr, mem, 0), c::kCopyRefused);
+  for (int off : {1, 4, 8, 15}) {
+    CHECK_EQ(c::copy_args(mem + off, mem + 32, 16), c::kCopyRefused);
+    CHECK_EQ(c::copy_args(mem, mem + 32 + off, 16), c::kCopyRefused);
+    CHECK_EQ(c::copy_args(mem + off, mem + 32, 0), c::kCopyRefused);
+  }
+}
+
 int main(int argc, char** argv) {
   std::vector<std::pair<const char*, std::function<void()>>> tests = {
       {"parse_size", test_parse_size},
@@ -1211,6 +1271,7 @@ int main(int argc, char** argv) {
       {"board", test_board},
       {"ledger_fresh", test_ledger_fresh},
       {"virtual_slots", test_virtual_slots},
+      {"calib_args", test_calib_args},
   };
   if (argc > 1 && !strcmp(argv[1], "--list")) {
     for (auto& t : tests) printf("%s\n", t.first);

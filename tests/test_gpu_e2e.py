@@ -132,7 +132,7 @@ def test_oversubscription_spills_past_hbm_share(tmp_region):
     res, _ = run_child("""
 import torch
 from amdvgpu.shim.region import Region
-from amdvgpu.ops import stream_copy
+from amdvgpu.ops import pattern_check, pattern_fill, stream_copy
 free, total = torch.cuda.mem_get_info(0)
 a = torch.ones(1536 << 20, dtype=torch.uint8, device="cuda")     # resident
 b = torch.full((1024 << 20,), 3, dtype=torch.uint8, device="cuda")  # crosses the share -> host
@@ -140,8 +140,9 @@ c = torch.full((1024 << 20,), 5, dtype=torch.uint8, device="cuda")  # host
 torch.cuda.synchronize()
 ok_ab = bool((a[:1 << 20] == 1).all()) and bool((b == 3).all()) and bool((c == 5).all())
 r = Region(os.environ["VGPU_SHARED_CACHE"]).device(0)
-# bandwidth of a kernel reading spilled memory
-dst = torch.empty_like(c)
+# bandwidth of a kernel reading spilled memory: every word of the source depends on its position
+pattern_fill(c, 0x5B111)
+dst = torch.zeros_like(c)
 stream_copy(dst, c); torch.cuda.synchronize()
 t0 = time.time()
 for _ in range(5): stream_copy(dst, c)
@@ -153,7 +154,7 @@ try:
 except torch.OutOfMemoryError:
     over = True
 emit(total=total, ok_ab=ok_ab, spilled=r["spilled"], used=r["used"], hbm=r["hbm_limit"], bw=bw, over=over,
-     ok=bool((dst == 5).all()))
+     ok=pattern_check(dst, 0x5B111) == (0, None) and pattern_check(c, 0x5B111) == (0, None))
 """, c)
     r = res[0]
     assert r["total"] == 8 * GiB
