@@ -6,6 +6,8 @@
                                          run CMD as a vGPU 'container' under the shim
     region   PATH [show|suspend|resume|set-limit DEV SIZE|set-cu DEV PCT|reclaim]
     devices  [--backend auto|sysfs|amdsmi|fake]   print the discovered GPUs as JSON
+    memprobe [--sizes 16k,1m,64m,2g] [--json]     load latency per working set and stream GB/s
+                                         of the GPU this process sees (under `run`: the slice)
 """
 import argparse
 import json
@@ -80,6 +82,58 @@ def _devices(argv):
     return 0
 
 
+def _memprobe(argv):
+    """Pointer-chase latency per working set (one lane per wave, one wave per CU the process
+    sees) and the read and write bandwidth of a 100 ms stream, alone in this process. It runs in
+    whatever environment it is started in: under ``amdvgpu run --cu 25 -- ...`` it measures the
+    slice."""
+    from .utils.sizes import parse_size
+    ap = argparse.ArgumentParser(prog="amdvgpu memprobe")
+    ap.add_argument("--sizes", default="16k,1m,64m,2g", help="working sets, powers of two from 256 to 4g")
+    ap.add_argument("--stream-bytes", default="1g", help="buffer of the timed stream")
+    ap.add_argument("--stream-ms", type=int, default=100)
+    ap.add_argument("--json", action="store_true")
+    a = ap.parse_args(argv)
+    sizes = [parse_size(x) for x in a.sizes.split(",") if x]
+    for n in sizes:
+        if n & (n - 1) or not 256 <= n <= 4 << 30:
+            ap.error(f"working set {n} is no power of two between 256 bytes and 4 GiB")
+    stream_bytes = parse_size(a.stream_bytes)
+    if not 0 <= a.stream_ms <= 1000:
+        ap.error("--stream-ms is 0..1000")
+    import torch
+    from .ops import mem_latency, mem_stream, pattern_fill
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    res = {"cus": cus, "latency": [], "stream": {}}
+    for n in sizes:
+        r = mem_latency(n)
+        r["cus"] = len(r["cus"])
+        res["latency"].append(r)
+        torch.cuda.empty_cache()
+    buf = torch.empty(stream_bytes // 4, dtype=torch.int32, device="cuda")
+    waves = min(16 * cus, 16384)
+    pattern_fill(buf, 1)
+    for mode in ("read", "write"):
+        mem_stream(buf, mode, waves, 0, 1, 1, check=False)              # one untimed pass
+        r = mem_stream(buf, mode, waves, a.stream_ms * 1000, 1 << 20, 1, check=False)
+        res["stream"][mode] = {"gbps": r["gbps"], "bytes": r["bytes"], "wall_s": r["wall_s"], "waves": waves,
+                               "passes_min": int(r["passes"].min()), "passes_max": int(r["passes"].max()),
+                               "cus": len(r["cus"])}
+    if a.json:
+        print(json.dumps(res))
+        return 0
+    print(f"{cus} CUs visible; one lane per wave, one wave per CU; median (p10 .. p90) over the chains")
+    for r in res["latency"]:
+        ns, cy = r["ns_per_load"], r["cycles_per_load"]
+        print(f"  {r['bytes']:>11} B  {ns['median']:8.1f} ns ({ns['p10']:.1f} .. {ns['p90']:.1f})  "
+              f"{cy['median']:8.1f} cycles ({cy['p10']:.1f} .. {cy['p90']:.1f})  per load; {r['chains']} chains x "
+              f"{r['steps']} steps on {r['cus']} CUs, {r['laps']:.3g} laps")
+    for mode, r in res["stream"].items():
+        print(f"  stream {mode:<5} {r['gbps']:8.1f} GB/s  ({r['bytes']} B in {r['wall_s'] * 1e3:.1f} ms, {r['waves']} waves "
+              f"on {r['cus']} CUs, {r['passes_min']}..{r['passes_max']} passes)")
+    return 0
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if not argv or argv[0] in ("-h", "--help"):
@@ -98,5 +152,7 @@ def main(argv=None):
         return _region(rest)
     if cmd == "devices":
         return _devices(rest)
+    if cmd == "memprobe":
+        return _memprobe(rest)
     print(f"unknown command {cmd!r}\n{__doc__}", file=sys.stderr)
     return 2

@@ -20,10 +20,18 @@ These are the measurement instruments of the data plane:
   the CU and SIMD it ran on: which CU of the slice, and which unit of it, computes wrong.
   :func:`selftest_reference` is the same definition in numpy; ``vgpu-validate --conformance
   --compute`` runs the same kernel in a pod.
+* :func:`ring_build` / :func:`mem_chase` / :func:`mem_latency` a pointer chase over a ring of
+  128-byte slots (native/include/vgpu/memprobe.h): dependent vector loads stamped with the
+  shader clock and the 100 MHz clock, the latency of whichever level of the memory hierarchy
+  the ring fits. :func:`ring_reference` and :func:`ring_jump` are the ring in numpy, and every
+  chain's end slot is checked against them.
+* :func:`mem_stream` waves that read or write their own chunk of a buffer for a fixed time: a
+  controlled memory load, checked against :func:`pattern_reference` word-exactly.
 
 The wrappers refuse with ValueError what the C entry points refuse with -1
 (native/include/vgpu/calib_args.h): no spin longer than a second or negative, no grid past
-2**20 workgroups, no copy of strided, misaligned, overlapping or host tensors.
+2**20 workgroups, no copy of strided, misaligned, overlapping or host tensors, no chase of more
+than 2**18 steps or 4096 workgroups, no stream longer than a second.
 
 The library is required: there is no PyTorch fallback, a missing build raises.
 """
@@ -57,6 +65,18 @@ def _k():
         L.vgpu_cu_selftest.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_int,
                                        C.c_void_p]
         L.vgpu_cu_selftest.restype = C.c_int
+        L.vgpu_ring_next.argtypes = [C.c_uint32, C.c_int, C.c_uint32]
+        L.vgpu_ring_next.restype = C.c_uint32
+        L.vgpu_ring_jump.argtypes = [C.c_uint32, C.c_uint64, C.c_int, C.c_uint32]
+        L.vgpu_ring_jump.restype = C.c_uint32
+        L.vgpu_ring_build.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
+        L.vgpu_ring_build.restype = C.c_int
+        L.vgpu_mem_chase.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint64,
+                                     C.c_void_p, C.c_void_p]
+        L.vgpu_mem_chase.restype = C.c_int
+        L.vgpu_mem_stream.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint32,
+                                      C.c_void_p, C.c_void_p]
+        L.vgpu_mem_stream.restype = C.c_int
         _lib = L
     return _lib
 
@@ -432,3 +452,303 @@ def cu_selftest(nblocks=2048, rounds=64, seed=0x5E1F7E57, hold_us=300, inject=()
     locs = np.unique(rec[:, 0]).tolist()
     return {"waves": nblocks * 4, "cus": {decode_location(c & 0xFFFF) for c in locs}, "simd_pairs": len(locs),
             "bad": wrong}
+
+
+# ---- the memory-system probe (native/include/vgpu/memprobe.h)
+
+RING_A = 0x9E3779B1
+RING_MIN_L, RING_MAX_L = 1, 25         # rings of 2**L slots of 128 bytes: 256 B .. 4 GiB
+RING_SLOT_BYTES = 128
+MAX_CHASE_BLOCKS = 4096
+MAX_CHASE_LANES = 64
+MAX_CHASE_STEPS = 1 << 18
+MAX_STREAM_WAVES = 16384
+MAX_STREAM_PASSES = 1 << 20
+CHASE_RECORD = 8                       # end slot, location, d(s_memtime) lo, hi, d(s_memrealtime), 0, 0, 0
+STREAM_RECORD = 8                      # passes, sum, location, d(s_memrealtime) lo, hi, 0, 0, 0
+
+
+def _ring_args(L, seed):
+    L, seed = int(L), int(seed)
+    if not RING_MIN_L <= L <= RING_MAX_L:
+        raise ValueError(f"L {L} outside {RING_MIN_L}..{RING_MAX_L}")
+    if not 0 <= seed <= _M32:
+        raise ValueError("seed is 32 bits")
+    return L, seed
+
+
+def _ring_c(seed):
+    return int(_selftest_hash(0x30000, seed)) | 1
+
+
+def ring_reference(L, seed):
+    """The ``next`` table of the pointer-chase ring in pure numpy: element i is word 0 of slot i,
+    ``(A * i + C) mod 2**L`` as uint32 (the definition of native/include/vgpu/memprobe.h)."""
+    import numpy as np
+    L, seed = _ring_args(L, seed)
+    i = np.arange(1 << L, dtype=np.uint64)
+    return ((i * np.uint64(RING_A) + np.uint64(_ring_c(seed))) & np.uint64((1 << L) - 1)).astype(np.uint32)
+
+
+def ring_jump(i, k, L, seed):
+    """The slot reached from slot ``i`` after ``k`` steps (``k`` is taken mod 2**64, which the
+    cycle's length divides): the affine map composed by squaring, as vgpu_ring_jump_slot. ``i``
+    and ``k`` may be numpy arrays (``k`` then uint64); scalars give a Python int."""
+    import numpy as np
+    L, seed = _ring_args(L, seed)
+    m32 = np.uint64(_M32)
+    scalar = np.ndim(i) == 0 and np.ndim(k) == 0
+    k = np.atleast_1d(np.asarray(k if np.ndim(k) else int(k) & (1 << 64) - 1, dtype=np.uint64)).copy()
+    i = np.asarray(i, dtype=np.uint64) & m32
+    ra, rc = np.ones_like(k), np.zeros_like(k)
+    pa, pc = np.uint64(RING_A), np.uint64(_ring_c(seed))
+    for _ in range(64):
+        odd = (k & np.uint64(1)).astype(bool)
+        rc = np.where(odd, (pa * rc + pc) & m32, rc)
+        ra = np.where(odd, (pa * ra) & m32, ra)
+        pc = (pa * pc + pc) & m32
+        pa = (pa * pa) & m32
+        k >>= np.uint64(1)
+    at = ((ra * i + rc) & np.uint64((1 << L) - 1)).astype(np.uint32)
+    return int(at[0]) if scalar else at
+
+
+def _probe_tensor(t, what, align, min_bytes):
+    nbytes = t.numel() * t.element_size()
+    if not t.is_contiguous():
+        raise ValueError(f"{what} needs a contiguous tensor")
+    if t.data_ptr() % align:
+        raise ValueError(f"{what} needs a {align}-byte aligned tensor")
+    if nbytes < min_bytes:
+        raise ValueError(f"{what} needs a tensor of at least {min_bytes} bytes")
+    if not t.is_cuda:
+        raise ValueError(f"{what} needs a CUDA tensor")
+    return nbytes
+
+
+def ring_build(t, L, seed):
+    """Writes the ring of ``2**L`` slots into tensor ``t`` (asynchronous): words 0 and 1 of every
+    128-byte slot, nothing else. ``t`` is a contiguous CUDA tensor, 128-byte aligned, of at
+    least ``128 << L`` bytes; ``L`` in 1..25. Anything else is a ValueError."""
+    import torch
+    L, seed = _ring_args(L, seed)
+    _probe_tensor(t, "ring_build", RING_SLOT_BYTES, RING_SLOT_BYTES << L)
+    rc = _k().vgpu_ring_build(C.c_void_p(t.data_ptr()), L, seed, _stream(torch, t.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_ring_build launch failed ({rc})")
+
+
+def mem_chase(ring, L, seed, nblocks, lanes, steps, first=0, chain_base=0, check=True, out=None):
+    """Pointer chase over a built ring: ``nblocks`` (1..4096) single-wave workgroups whose lanes
+    ``l < lanes`` (1..64) each make ``steps`` (1..2**18) dependent loads. Lane l of block b is
+    chain ``g = chain_base + 64 * b + l`` and starts ``g * steps`` steps after slot ``first``, so
+    consecutive chains tile the cycle, and a later launch with a larger ``chain_base`` touches
+    fresh lines. Synchronises.
+
+    Returns ``records`` (uint32 [nblocks * 64, 8]: end slot, location with SIMD, the s_memtime
+    difference lo and hi, the s_memrealtime difference in 10 ns ticks, three zeros; rows of lanes
+    >= ``lanes`` are not written), ``expected`` (uint32 [nblocks, lanes], every chain's end from
+    :func:`ring_jump`), ``cycles`` and ``ticks`` ([nblocks, lanes]) and ``wall_s``, the host's
+    clock around launch and synchronize. Unless ``check`` is false, a chain whose end differs
+    raises RuntimeError naming it. ``out`` may give the int32 CUDA tensor of ``nblocks * 512``
+    elements that the kernel writes."""
+    import time
+    import numpy as np
+    import torch
+    L, seed = _ring_args(L, seed)
+    nblocks, lanes, steps, first, chain_base = int(nblocks), int(lanes), int(steps), int(first), int(chain_base)
+    if not 1 <= nblocks <= MAX_CHASE_BLOCKS:
+        raise ValueError(f"nblocks {nblocks} outside 1..{MAX_CHASE_BLOCKS}")
+    if not 1 <= lanes <= MAX_CHASE_LANES:
+        raise ValueError(f"lanes {lanes} outside 1..{MAX_CHASE_LANES}")
+    if not 1 <= steps <= MAX_CHASE_STEPS:
+        raise ValueError(f"steps {steps} outside 1..{MAX_CHASE_STEPS}")
+    if not 0 <= first < 1 << L:
+        raise ValueError(f"first {first} outside the ring")
+    if not 0 <= chain_base < 1 << 64:
+        raise ValueError("chain_base is 64 bits")
+    _probe_tensor(ring, "mem_chase", RING_SLOT_BYTES, RING_SLOT_BYTES << L)
+    words = nblocks * 64 * CHASE_RECORD
+    if out is None:
+        out = torch.zeros(words, dtype=torch.int32, device=ring.device)
+    elif out.dtype != torch.int32 or out.numel() != words or out.device != ring.device:
+        raise ValueError(f"out is an int32 tensor of {words} elements on the ring's device")
+    else:
+        _probe_tensor(out, "mem_chase", 4, 4 * words)
+    torch.cuda.synchronize(ring.device)
+    t0 = time.perf_counter()
+    rc = _k().vgpu_mem_chase(C.c_void_p(ring.data_ptr()), L, seed, nblocks, lanes, steps, first, chain_base,
+                             C.c_void_p(out.data_ptr()), _stream(torch, ring.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_mem_chase launch failed ({rc})")
+    torch.cuda.synchronize(ring.device)
+    wall = time.perf_counter() - t0
+    rec = out.cpu().numpy().view(np.uint32).reshape(nblocks * 64, CHASE_RECORD)
+    g = (np.uint64(chain_base) + np.arange(nblocks * 64, dtype=np.uint64).reshape(nblocks, 64)[:, :lanes])
+    with np.errstate(over="ignore"):
+        k = (g + np.uint64(1)) * np.uint64(steps)        # wraps mod 2**64, as the kernel's product does
+    expected = ring_jump(first, k.reshape(-1), L, seed).reshape(nblocks, lanes)
+    used = rec.reshape(nblocks, 64, CHASE_RECORD)[:, :lanes]
+    if check:
+        bad = np.argwhere(used[:, :, 0] != expected)
+        if len(bad):
+            b, l = (int(x) for x in bad[0])
+            raise RuntimeError(f"mem_chase: chain {chain_base + 64 * b + l} (block {b}, lane {l}) ended at slot "
+                               f"{int(used[b, l, 0])}, expected {int(expected[b, l])}; {len(bad)} chains differ")
+    cycles = used[:, :, 2].astype(np.uint64) | used[:, :, 3].astype(np.uint64) << np.uint64(32)
+    return {"records": rec, "expected": expected, "cycles": cycles, "ticks": used[:, :, 4].astype(np.uint64),
+            "wall_s": wall}
+
+
+def chase_steps(n, nblocks, warm):
+    """The steps :func:`mem_latency` gives every chain of a one-lane launch over a ring of ``n``
+    slots. With one lane, block b is chain ``64 * b`` and starts ``64 * b * steps`` slots along the
+    cycle, so a power-of-two ``steps >= n / 64`` would start every chain at the same slot.
+
+    * cold: ``n / (64 * nblocks)``: the chains lie ``n / nblocks`` apart, each walks the first
+      64th of its stretch, and ``chain_base`` 1..63 walk the others.
+    * warm, up to 2**18 slots: ``n``, every chain walks the whole ring.
+    * warm, above: ``steps = t * n / 64 + d / 64`` with ``d = n / nblocks`` (down to a multiple of
+      64) and ``t = ceil(64 / nblocks)``: then ``64 * steps = d (mod n)``, the chains start ``d``
+      apart and each walks at least ``d`` slots, so together they cover the ring.
+
+    At least 1024 (a few hundred microseconds) and at most 2**18."""
+    n, nblocks = int(n), int(nblocks)
+    if not warm:
+        steps = n // (64 * nblocks)
+    elif n <= MAX_CHASE_STEPS:
+        steps = n
+    else:
+        steps = -(-64 // nblocks) * (n // 64) + (n // nblocks // 64 * 64) // 64
+    return min(max(steps, 1024), MAX_CHASE_STEPS)
+
+
+def mem_latency(nbytes, steps=None, nblocks=None, lanes=1, warm=None, seed=0x3E3F20BE, chain_base=0, ring=None,
+                device=None):
+    """Load-to-use latency over a working set of ``nbytes`` (a power of two, 256 B .. 4 GiB):
+    allocates and builds the ring (or takes a built ``ring`` of that size and seed), makes one
+    identical untimed launch when ``warm``, then the timed one.
+
+    ``nblocks`` defaults to the CUs the device reports (one wave per CU of a slice) and ``steps``
+    to :func:`chase_steps`: a warm launch covers the whole ring, a cold one walks every line
+    once. ``warm`` defaults to true up to 256 MiB, the size of the Infinity Cache, and
+    to false above: there a warm launch would only leave the few lines it touched in the caches,
+    and the figure would be theirs. A cold launch with the next ``chain_base`` (add 1, up to 63,
+    with one lane) walks lines that no earlier one has touched.
+
+    Returns ``ns_per_load`` and ``cycles_per_load`` as ``{median, p10, p90}`` over the chains,
+    ``cus`` (the set of (xcc, se, sh, cu) the waves ran on), ``chains``, ``steps``, ``warm`` and
+    ``laps = steps / n``."""
+    import numpy as np
+    import torch
+    nbytes = int(nbytes)
+    L = nbytes.bit_length() - 1 - 7
+    if nbytes != RING_SLOT_BYTES << max(L, 0) or not RING_MIN_L <= L <= RING_MAX_L:
+        raise ValueError("the working set is a power of two between 256 bytes and 4 GiB")
+    device = torch.device(device or (ring.device if ring is not None else "cuda"))
+    if nblocks is None:
+        nblocks = min(torch.cuda.get_device_properties(device).multi_processor_count, MAX_CHASE_BLOCKS)
+    n = 1 << L
+    if warm is None:
+        warm = nbytes <= 256 << 20
+    if steps is None:
+        steps = chase_steps(n, nblocks, warm)
+    if ring is None:
+        ring = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+        ring_build(ring, L, seed)
+    if warm:
+        mem_chase(ring, L, seed, nblocks, lanes, steps, chain_base=chain_base)
+    r = mem_chase(ring, L, seed, nblocks, lanes, steps, chain_base=chain_base)
+
+    def spread(x):
+        return {"median": float(np.median(x)), "p10": float(np.percentile(x, 10)), "p90": float(np.percentile(x, 90))}
+
+    locs = np.unique(r["records"].reshape(int(nblocks), 64, CHASE_RECORD)[:, :int(lanes), 1])
+    return {"bytes": nbytes, "L": L, "chains": int(nblocks) * int(lanes), "steps": int(steps), "laps": int(steps) / n,
+            "warm": bool(warm),
+            "ns_per_load": spread(r["ticks"].astype(np.float64) * 10.0 / steps),
+            "cycles_per_load": spread(r["cycles"].astype(np.float64) / steps),
+            "cus": {decode_location(int(c) & 0xFFFF) for c in locs}, "wall_s": r["wall_s"]}
+
+
+def stream_chunks(n_vec, waves):
+    """(begin, length) of every wave's chunk, in 16-byte vectors: ``n_vec // waves`` each and
+    the first ``n_vec % waves`` waves one more."""
+    import numpy as np
+    q, r = divmod(int(n_vec), int(waves))
+    w = np.arange(int(waves), dtype=np.int64)
+    return w * q + np.minimum(w, r), q + (w < r).astype(np.int64)
+
+
+def mem_stream(t, mode, waves, duration_us, max_passes, seed, base=0, check=True, out=None):
+    """A controlled memory load for a fixed time: ``waves`` (1..16384, a multiple of 4) waves
+    sweep tensor ``t`` (at least ``waves`` 16-byte vectors), each its own contiguous chunk, pass
+    after pass for ``duration_us`` (0..1000000; 0 is exactly one pass) or ``max_passes``
+    (1..2**20) passes. ``mode`` 0 (or "read") reads with non-temporal loads, 1 (or "write") writes
+    the pattern of ``(base, seed)`` with non-temporal stores. Synchronises.
+
+    Returns ``passes`` and ``ticks`` per wave, ``bytes`` moved in all, ``wall_s`` and ``gbps``
+    over the host's clock around launch and synchronize, ``records`` (uint32 [waves, 8]) and
+    ``cus``. With ``check``, read mode expects ``t`` to hold :func:`pattern_fill` of ``(seed,
+    base)`` and verifies every wave's sum against ``passes * chunk_sum`` from
+    :func:`pattern_reference`, write mode verifies the buffer with :func:`pattern_check`; a
+    failure raises RuntimeError naming the wave (or the word)."""
+    import time
+    import numpy as np
+    import torch
+    mode = {"read": 0, "write": 1}.get(mode, mode)
+    if mode not in (0, 1):
+        raise ValueError("mode is 0 / 'read' or 1 / 'write'")
+    waves, duration_us, max_passes, seed, base = int(waves), int(duration_us), int(max_passes), int(seed), int(base)
+    if not 1 <= waves <= MAX_STREAM_WAVES or waves % 4:
+        raise ValueError(f"waves {waves} outside 1..{MAX_STREAM_WAVES} or no multiple of 4")
+    if not 0 <= duration_us <= MAX_SPIN_US:
+        raise ValueError(f"duration_us {duration_us} outside 0..{MAX_SPIN_US}")
+    if not 1 <= max_passes <= MAX_STREAM_PASSES:
+        raise ValueError(f"max_passes {max_passes} outside 1..{MAX_STREAM_PASSES}")
+    if not 0 <= seed <= _M32 or not 0 <= base < 1 << 64:
+        raise ValueError("seed is 32 bits, base 64")
+    nbytes = t.numel() * t.element_size()
+    if nbytes % 16:
+        raise ValueError("mem_stream needs a multiple of 16 bytes")
+    n_vec = nbytes // 16
+    if n_vec < waves:
+        raise ValueError(f"mem_stream needs at least one 16-byte vector per wave: n_vec {n_vec} < waves {waves}")
+    _probe_tensor(t, "mem_stream", 16, 16)
+    words = waves * STREAM_RECORD
+    if out is None:
+        out = torch.zeros(words, dtype=torch.int32, device=t.device)
+    elif out.dtype != torch.int32 or out.numel() != words or out.device != t.device:
+        raise ValueError(f"out is an int32 tensor of {words} elements on the buffer's device")
+    else:
+        _probe_tensor(out, "mem_stream", 16, 4 * words)
+    torch.cuda.synchronize(t.device)
+    t0 = time.perf_counter()
+    rc = _k().vgpu_mem_stream(C.c_void_p(t.data_ptr()), n_vec, mode, waves, duration_us, max_passes, base, seed,
+                              C.c_void_p(out.data_ptr()), _stream(torch, t.device))
+    if rc != 0:
+        raise RuntimeError(f"vgpu_mem_stream launch failed ({rc})")
+    torch.cuda.synchronize(t.device)
+    wall = time.perf_counter() - t0
+    rec = out.cpu().numpy().view(np.uint32).reshape(waves, STREAM_RECORD)
+    passes = rec[:, 0].astype(np.int64)
+    begin, length = stream_chunks(n_vec, waves)
+    if check and mode == 0:
+        ref = pattern_reference(4 * n_vec, seed, base).astype(np.uint64)
+        chunk = np.add.reduceat(ref, 4 * begin) & np.uint64(_M32)
+        want = (chunk * passes.astype(np.uint64)) & np.uint64(_M32)
+        bad = np.flatnonzero(rec[:, 1] != want)
+        if len(bad):
+            w = int(bad[0])
+            raise RuntimeError(f"mem_stream: wave {w} summed {int(rec[w, 1]):#x} over {int(passes[w])} passes of vectors "
+                               f"{int(begin[w])}..{int(begin[w] + length[w])}, expected {int(want[w]):#x}; "
+                               f"{len(bad)} waves differ")
+    if check and mode == 1:
+        mismatches, first = pattern_check(t, seed, base)
+        if mismatches:
+            raise RuntimeError(f"mem_stream: {mismatches} words differ from the pattern after a write, the first is "
+                               f"word {first}")
+    total = int((passes * length).sum()) * 16
+    ticks = rec[:, 3].astype(np.uint64) | rec[:, 4].astype(np.uint64) << np.uint64(32)
+    return {"passes": passes, "ticks": ticks, "bytes": total, "wall_s": wall, "gbps": total / wall / 1e9,
+            "records": rec, "cus": {decode_location(int(c) & 0xFFFF) for c in np.unique(rec[:, 2])}}

@@ -13,6 +13,13 @@
 //   scratch_hog  stride odd and > 0; out non-null
 //   stream_copy  bytes a multiple of 16; both pointers non-null and 16-byte aligned;
 //                bytes == 0 is accepted and launches nothing
+//   ring_build   L in 1 .. 25 (vgpu/memprobe.h); the ring non-null and 128-byte aligned
+//   mem_chase    L in 1 .. 25; nblocks in 1 .. 4096; lanes in 1 .. 64; steps in 1 .. 2^18 (under
+//                about a second even at a few us per load: a ring in spilled host memory, or
+//                contention); ring and out non-null
+//   mem_stream   mode 0 (read) or 1 (write); waves in 1 .. 16384 and a multiple of 4;
+//                n_vec >= waves; duration_us in 0 .. 1 000 000 (its ticks are spin_ticks, clamped);
+//                max_passes in 1 .. 2^20; buffer and out non-null and 16-byte aligned
 #pragma once
 
 #include <cstddef>
@@ -54,6 +61,30 @@ enum CopyArgs { kCopyRefused = -1, kCopyNothing = 0, kCopyLaunch = 1 };
 inline CopyArgs copy_args(const void* dst, const void* src, size_t bytes) {
   if (!dst || !src || ((uintptr_t)dst & 15) || ((uintptr_t)src & 15) || (bytes & 15)) return kCopyRefused;
   return bytes ? kCopyLaunch : kCopyNothing;
+}
+
+constexpr int kMinRingL = 1;
+constexpr int kMaxRingL = 25;
+constexpr int kMaxChaseBlocks = 4096;
+constexpr int kMaxChaseLanes = 64;
+constexpr int kMaxChaseSteps = 1 << 18;
+constexpr int kMaxStreamWaves = 16384;
+constexpr int kMaxStreamPasses = 1 << 20;
+
+inline bool ring_l_ok(int L) { return L >= kMinRingL && L <= kMaxRingL; }
+
+inline bool ring_build_args_ok(const void* ring, int L) { return ring && !((uintptr_t)ring & 127) && ring_l_ok(L); }
+
+inline bool chase_args_ok(const void* ring, int L, int nblocks, int lanes, int steps, const void* out) {
+  return ring && out && ring_l_ok(L) && nblocks >= 1 && nblocks <= kMaxChaseBlocks && lanes >= 1 &&
+         lanes <= kMaxChaseLanes && steps >= 1 && steps <= kMaxChaseSteps;
+}
+
+inline bool stream_args_ok(const void* buf, uint64_t n_vec, int mode, int waves, int duration_us, int max_passes,
+                           const void* out) {
+  return buf && out && !((uintptr_t)buf & 15) && !((uintptr_t)out & 15) && (mode == 0 || mode == 1) && waves >= 1 &&
+         waves <= kMaxStreamWaves && !(waves & 3) && n_vec >= (uint64_t)waves && spin_us_ok(duration_us) &&
+         max_passes >= 1 && max_passes <= kMaxStreamPasses;
 }
 
 }  // namespace calib

@@ -24,16 +24,23 @@
 //                     vgpu/selftest.h (VALU, LDS, i8 and f16 MFMA) and records where it ran and
 //                     its four words, then holds its CU like the census: which CU, and which
 //                     unit of it, computes wrong (the kernel is device_kernels.h as well).
+//  * vgpu_ring_build / vgpu_mem_chase  a ring of 128-byte slots linked by a full-period affine
+//                     map (vgpu/memprobe.h) and a pointer chase over it: dependent vector loads
+//                     between s_memtime / s_memrealtime stamps, every chain's end slot known to
+//                     the host. The latency of whichever level of the hierarchy the ring fits.
+//  * vgpu_mem_stream  waves that read or write a chunk of their own for a fixed time with
+//                     non-temporal 16-byte accesses: a controlled memory load, word-exact.
 //
 // C ABI, loaded with ctypes; pointers are device pointers (e.g. torch data_ptr()) and
 // `stream` is a hipStream_t (torch.cuda.current_stream().cuda_stream). What each entry point
-// accepts is vgpu/calib_args.h (host-only, tested in tests/core_tests.cpp).
+// accepts is vgpu/calib_args.h (host-only, tested in tests/core_tests.cpp and tests/memprobe_host.cpp).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "device_kernels.h"
 #include "vgpu/calib_args.h"
+#include "vgpu/memprobe.h"
 
 namespace calib = vgpu::calib;
 
@@ -77,6 +84,108 @@ __global__ void __launch_bounds__(256) copy_kernel(u32x4* __restrict__ dst, cons
   size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   size_t stride = (size_t)gridDim.x * blockDim.x;
   for (; i < n; i += stride) dst[i] = __builtin_nontemporal_load(&src[i]);
+}
+
+// ---- the memory-system probe (vgpu/memprobe.h)
+
+using u32x2 = unsigned int __attribute__((ext_vector_type(2)));
+
+constexpr unsigned kChaseRecord = 8;   // end slot, location, d(s_memtime) lo, hi, d(s_memrealtime), 0, 0, 0
+constexpr unsigned kStreamRecord = 8;  // passes, sum, location, d(s_memrealtime) lo, hi, 0, 0, 0
+
+// Census code plus SIMD id, as cu_selftest records it.
+__device__ inline uint32_t location_with_simd() {
+  const uint32_t hw = __builtin_amdgcn_s_getreg(vgpu_dev::kHwRegHwId | (0u << 6) | (31u << 11));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(vgpu_dev::kHwRegXccId | (0u << 6) | (3u << 11));
+  return ((hw >> 4) & 0x3) << 16 | (xcc & 0xf) << 12 | ((hw >> 13) & 0x7) << 8 | ((hw >> 12) & 0x1) << 4 | ((hw >> 8) & 0xf);
+}
+
+// Words 0 and 1 of every slot, one 8-byte store per slot; words 2..31 are left alone.
+__global__ void __launch_bounds__(256) ring_build_kernel(uint32_t* __restrict__ ring, uint32_t L, uint32_t seed) {
+  const uint64_t n = 1ull << L, stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    u32x2 v;
+    v.x = vgpu_ring_next_slot((uint32_t)i, L, seed);
+    v.y = (uint32_t)i ^ seed;
+    *reinterpret_cast<u32x2*>(ring + i * VGPU_RING_SLOT_WORDS) = v;
+  }
+}
+
+// Single-wave workgroups; lane l < lanes of block b walks chain g = chain_base + 64 b + l from
+// next^(g * steps)(first). The start depends on threadIdx.x, so the address is not uniform and
+// the loads are vector loads (global_load_dword, the vector L1 -> L2 path of a tenant's kernel)
+// and not scalar ones. `& mask` keeps a corrupted ring inside the buffer.
+__global__ void __launch_bounds__(64)
+mem_chase_kernel(const uint32_t* ring, uint32_t L, uint32_t seed, uint32_t lanes, uint32_t steps, uint32_t first,
+                 uint64_t chain_base, uint32_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x;
+  if (lane >= lanes) return;
+  const uint64_t g = chain_base + 64ull * blockIdx.x + lane;
+  const uint32_t mask = vgpu_ring_mask(L);
+  uint32_t at = vgpu_ring_jump_slot(first & mask, g * steps, L, seed);
+  // the start and the ring's address are there before the opening stamps (the pointer is an input
+  // only: passed through the asm it would lose its address space, and the loads would be flat ones)
+  asm volatile("" : "+v"(at) : "s"(ring));
+  const uint64_t c0 = __builtin_amdgcn_s_memtime();
+  const uint64_t r0 = __builtin_amdgcn_s_memrealtime();
+  for (uint32_t s = 0; s < steps; s++) at = ring[(uint64_t)at * VGPU_RING_SLOT_WORDS] & mask;
+  // the closing stamps follow the last load's arrival: without this its wait may sink below them
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(at) : "memory");
+  const uint64_t c1 = __builtin_amdgcn_s_memtime();
+  const uint64_t r1 = __builtin_amdgcn_s_memrealtime();
+  const uint64_t dc = c1 - c0;
+  uint32_t* rec = out + ((uint64_t)blockIdx.x * 64 + lane) * kChaseRecord;
+  rec[0] = at;
+  rec[1] = location_with_simd();
+  rec[2] = (uint32_t)dc;
+  rec[3] = (uint32_t)(dc >> 32);
+  rec[4] = (uint32_t)(r1 - r0);
+  rec[5] = rec[6] = rec[7] = 0;
+}
+
+// The unit is the wave: wave w of `waves` owns n_vec / waves consecutive 16-byte vectors (the
+// first n_vec % waves waves one more) and sweeps them, 16 bytes per lane, pass after pass until
+// `ticks` of the 100 MHz clock have gone by or `max_passes` are done. Every wave reads the clock
+// itself (a scalar read), so the loop condition is wave-uniform and needs no barrier; a pass
+// once begun is finished, so ticks = 0 is exactly one pass.
+__global__ void __launch_bounds__(256)
+mem_stream_kernel(vgpu_dev::u32x4* buf, uint64_t n_vec, uint32_t waves, uint32_t mode, uint64_t ticks, uint32_t max_passes,
+                  uint64_t base, uint32_t seed, uint32_t* __restrict__ out) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint64_t w = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (w >= waves) return;
+  const uint64_t q = n_vec / waves, r = n_vec % waves;
+  const uint64_t begin = w * q + (w < r ? w : r), len = q + (w < r ? 1 : 0);
+  const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+  uint64_t dt;
+  uint32_t passes = 0, sum = 0;
+  do {
+    asm volatile("" ::: "memory");  // every pass touches memory again
+    if (mode == 0) {
+#pragma unroll 4
+      for (uint64_t i = lane; i < len; i += 64) {
+        const vgpu_dev::u32x4 v = __builtin_nontemporal_load(&buf[begin + i]);
+        sum += v.x + v.y + v.z + v.w;
+      }
+    } else {
+      for (uint64_t i = lane; i < len; i += 64)
+        __builtin_nontemporal_store(vgpu_dev::pattern_vec(base + 4 * (begin + i), seed), &buf[begin + i]);
+    }
+    passes++;
+    dt = __builtin_amdgcn_s_memrealtime() - t0;
+  } while (passes < max_passes && dt < ticks);
+  sum = vgpu_dev::wave_sum(sum);
+  asm volatile("s_waitcnt vmcnt(0)" ::"v"(sum) : "memory");  // the last loads and stores have landed
+  dt =__builtin_amdgcn_s_memrealtime() - t0;
+  if (lane == 0) {
+    uint32_t* rec = out + w * kStreamRecord;
+    rec[0] = passes;
+    rec[1] = sum;
+    rec[2] = location_with_simd();
+    rec[3] = (uint32_t)dt;
+    rec[4] = (uint32_t)(dt >> 32);
+    rec[5] = rec[6] = rec[7] = 0;
+  }
 }
 
 }  // namespace
@@ -174,6 +283,49 @@ int vgpu_cu_selftest(uint32_t* out, int nblocks, uint32_t seed, int rounds, int 
     return -1;
   hipLaunchKernelGGL(cu_selftest, dim3(nblocks), dim3(64 * vgpu_dev::kSelftestWaves), 0, (hipStream_t)stream, out, seed,
                      (uint32_t)rounds, (uint64_t)hold_us * 100, bad, (uint32_t)n_bad);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// The ring of vgpu/memprobe.h, on the host: no HIP call.
+uint32_t vgpu_ring_next(uint32_t i, int L, uint32_t seed) {
+  return calib::ring_l_ok(L) ? vgpu_ring_next_slot(i, (uint32_t)L, seed) : ~0u;
+}
+
+// The slot `k` steps after `i`; ~0 for an L outside 1..25.
+uint32_t vgpu_ring_jump(uint32_t i, uint64_t k, int L, uint32_t seed) {
+  return calib::ring_l_ok(L) ? vgpu_ring_jump_slot(i, k, (uint32_t)L, seed) : ~0u;
+}
+
+// Writes words 0 and 1 of the 2^L slots of 128 bytes at `ring` (128-byte aligned, L in 1..25).
+int vgpu_ring_build(void* ring, int L, uint32_t seed, void* stream) {
+  if (!calib::ring_build_args_ok(ring, L)) return -1;
+  hipLaunchKernelGGL(ring_build_kernel, dim3(vgpu_dev::pattern_blocks(1ull << L)), dim3(vgpu_dev::kPatternBlock), 0,
+                     (hipStream_t)stream, (uint32_t*)ring, (uint32_t)L, seed);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// `nblocks` (1..4096) single-wave workgroups; lane l < lanes (1..64) of block b makes `steps`
+// (1..2^18) dependent loads from slot next^((chain_base + 64 b + l) * steps)(first) of a built
+// ring and writes eight words at out[(64 b + l) * 8]: end slot, location with SIMD, the
+// s_memtime difference (lo, hi), the s_memrealtime difference, three zeros. out holds
+// nblocks * 512 uint32; lanes >= `lanes` write nothing.
+int vgpu_mem_chase(const void* ring, int L, uint32_t seed, int nblocks, int lanes, int steps, uint32_t first,
+                   uint64_t chain_base, uint32_t* out, void* stream) {
+  if (!calib::chase_args_ok(ring, L, nblocks, lanes, steps, out)) return -1;
+  hipLaunchKernelGGL(mem_chase_kernel, dim3(nblocks), dim3(64), 0, (hipStream_t)stream, (const uint32_t*)ring, (uint32_t)L,
+                     seed, (uint32_t)lanes, (uint32_t)steps, first, chain_base, out);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// `waves` (1..16384, a multiple of 4) waves sweep the `n_vec` (>= waves) 16-byte vectors at buf
+// for `duration_us` (0..1000000) or `max_passes` (1..2^20) passes, reading (mode 0) or writing
+// the pattern of (base, seed) (mode 1). Wave w writes eight words at out[8 w]: passes, sum of all
+// words read (0 in write mode), location with SIMD, the s_memrealtime difference (lo, hi), three zeros.
+int vgpu_mem_stream(void* buf, uint64_t n_vec, int mode, int waves, int duration_us, int max_passes, uint64_t base,
+                    uint32_t seed, uint32_t* out, void* stream) {
+  if (!calib::stream_args_ok(buf, n_vec, mode, waves, duration_us, max_passes, out)) return -1;
+  hipLaunchKernelGGL(mem_stream_kernel, dim3(waves / 4), dim3(256), 0, (hipStream_t)stream, (vgpu_dev::u32x4*)buf, n_vec,
+                     (uint32_t)waves, (uint32_t)mode, calib::spin_ticks(duration_us), (uint32_t)max_passes, base, seed, out);
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
